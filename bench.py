@@ -1,10 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- clips/s for one full G + D_s + D_t training step (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: re-executes itself under
-                                                               torch.distributed.run, one rank per GPU, RCCL;
-                                                               defaults: N = 1, K = 10, W = 3 -- about a minute incl. cpu_baseline)
+    python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: runs N ranks of this script in
+                                                               child processes under torch.distributed.run, one rank per GPU,
+                                                               RCCL; defaults: N = 1, K = 10, W = 3)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                                (+ the `roofline` and `cpu_baseline` objects below: one extra
+                                                               instrumented step and the CPU oracle, about a minute more)
+    python bench.py ... --dump-outputs DIR                    (after the timed steps: what the last timed step returned and
+                                                               left behind, as DIR/<name>.npy -- see dump_outputs())
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`ms_per_step` = wall time of one timed step);
+everything else it can measure is behind --full.
 
 Workload (BASELINE.json configs[1], per GPU): UCF-101-shaped synthetic clips, T=48, 64x64,
 101 classes, ch=32, z_dim=120, k_sample=8, hinge, Adam(5e-5, (0, 0.9)), batch 64 per GPU, bf16
@@ -13,7 +20,7 @@ averaged with RCCL; `value` = N*64 / (max over ranks of the step time).
 Other shapes: --size 128 --n-class 600 (configs[3]; the batch defaults to the largest of 64 / 48 / 32 / 16 that fits),
 --frames 12 --size 128 --state-carry (configs[4]: initial ConvGRU states supplied and differentiated).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line with --full:
   roofline      dominant kernel family (conv_halo / conv_igemm bf16: forward + backward-data launches) --
                 algorithmic FLOPs of its launches / their summed durations, measured with HIP
                 events recorded on the launch stream around every launch of ONE EXTRA step run after the timed region
@@ -67,9 +74,18 @@ def parse():
     ap.add_argument("--force-exchange", action="store_true",
                     help="N=1 only: create a ONE-rank RCCL group and run the whole data-parallel exchange (all-reduces on the exchange "
                          "stream, bucket hooks, side-stream fences) -- prices the exchange's fences / host work at this batch size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-prof", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline step and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-prof", action="store_true", help="--full without the instrumented roofline step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 def respawn_if_needed(a):
@@ -145,6 +161,35 @@ def carried_states(a, batch, dev):
     return [[torch.randn(batch, h, s, s, device=dev, requires_grad=True) for h in (c, 2 * c, c)] for c, s in sizes]
 
 
+DUMP_VALUES = 12 << 20       # at most 48 MB of sampled network state in a --dump-outputs directory
+
+
+def dump_outputs(d, losses, tr):
+    """What a caller of train_step() has after the last timed step: the six loss terms it returned (losses.npy, float64:
+    ds_real, ds_fake, dt_real, dt_fake, g_s, g_t) and the state the step left in the three networks (<net>_state.npy,
+    float32: every floating state_dict entry in state_dict order, flattened).  An entry larger than `per` values
+    (min(65536, DUMP_VALUES / number of entries)) contributes the values at `per` sorted indices drawn without replacement
+    from a generator seeded with the entry's position, so the sample is the same in every run of the same configuration.
+    Called before anything else runs on the networks (the --full roofline step trains one more step)."""
+    import numpy as np
+    nets = (("G", tr.G), ("D_s", tr.D_s), ("D_t", tr.D_t))
+    states = [(tag, [v.detach() for v in net.state_dict().values() if v.is_floating_point()]) for tag, net in nets]
+    per = min(65536, DUMP_VALUES // sum(len(vs) for _, vs in states))
+    out = {"losses": np.array([float(v.detach()) for v in losses], dtype=np.float64)}
+    for tag, vs in states:
+        parts = []
+        for i, v in enumerate(vs):
+            flat = v.reshape(-1)
+            if flat.numel() > per:
+                idx = np.sort(np.random.default_rng(i).choice(flat.numel(), per, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            parts.append(flat.float().cpu().numpy())
+        out[tag + "_state"] = np.concatenate(parts).astype(np.float32)
+    os.makedirs(d, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(d, name + ".npy"), arr)
+
+
 def main():
     a = parse()
     if a.force_exchange:
@@ -215,7 +260,10 @@ def main():
     sync()
     dt = time.perf_counter() - t0               # exactly K steps in the execution mode training runs in
     lossv = [float(v.detach()) for v in losses]
-    if not a.no_kernel_prof:
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, losses, tr)
+    kernel_prof = a.full and not a.no_kernel_prof
+    if kernel_prof:
         # One EXTRA step after the timed region (not part of `value`): HIP events around every conv launch, recorded on the
         # launch stream, with the weight-gradient kernels on the launch stream as well instead of beside it -- a kernel's
         # duration is taken while it has the GPU to itself.
@@ -233,7 +281,7 @@ def main():
     value = gB * a.steps / dt
 
     roof = None
-    if not a.no_kernel_prof:
+    if kernel_prof:
         lib.dvd_prof_report_variants.restype = C.c_longlong
         res, by_kernel = {}, {}
         # bf16: the halo-staged kernels read their weights from L2 (conv_halo_gb_kernel; conv_halo_gbs_kernel on 4x4 / 8x8 frames);
@@ -296,7 +344,7 @@ def main():
                "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}
         if roof:
             out["roofline"] = roof
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

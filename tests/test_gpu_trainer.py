@@ -300,6 +300,15 @@ def _cos(a, b):
 F14_NUMBERS = {}
 
 
+def _record(name, obj):
+    """Measured numbers for the record: written to $DVD_TEST_NUMBERS_DIR/<name> when that names a directory, else nowhere."""
+    import json, os
+    d = os.environ.get("DVD_TEST_NUMBERS_DIR")
+    if d and os.path.isdir(d):
+        with open(os.path.join(d, name), "w") as f:
+            json.dump(obj, f, indent=1)
+
+
 @pytest.mark.parametrize("mode", ["exact", "bf16", "ulp"])
 def test_step_at_reference_default_init(golden, mode):
     """ONE step from the reference's own default initialisation (orthogonal ConvGRU weights: the state a fresh model starts
@@ -315,7 +324,6 @@ def test_step_at_reference_default_init(golden, mode):
               that the bf16 mode's loss errors and generator-gradient misalignment (1 - cosine) stay within 3x the
               one-ulp run's (+ 1e-3), i.e. the 0.94 is the conditioning of the recurrence at this initialisation, not
               kernel error."""
-    import json, os
     g = golden("f14_default_init_bf16")
     exact = mode != "bf16"
     tr, _ = make_trainer(g, g, "hinge", torch.float32 if exact else torch.bfloat16)
@@ -341,9 +349,7 @@ def test_step_at_reference_default_init(golden, mode):
         rec[f"cos_min_{tag}"] = min(cs.values())
         rec[f"cos_{tag}"] = cs
     F14_NUMBERS[mode] = rec
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/f14_numbers.json", "w") as f:
-        json.dump(F14_NUMBERS, f, indent=1)
+    _record("f14_numbers.json", F14_NUMBERS)
     if mode == "exact":
         np.testing.assert_allclose(losses, want, rtol=2e-3, atol=2e-4)
         for tag in ("Ds", "Dt", "G"):
@@ -371,7 +377,6 @@ def test_bf16_trajectory_follows_exact_mode(golden):
     through fp32 atomics, so even two exact-mode runs part in the fourth digit after 20 Adam steps; round 3 quoted 1e-2 from a
     single run at 4.1e-3 and the bound then failed about one run in four), and the parameter displacement of the two runs (both have moved every weight by ~20 Adam steps of 5e-5)
     agreeing to cosine >= 0.99 for each network (measured 0.9995 / 0.99999 / 0.99999)."""
-    import json, os
     g = golden("f14_default_init_bf16")
     ch, T, k, B, n_class, steps, z_dim = [int(v) for v in g["meta.cfg"]]
     runs = {}
@@ -392,10 +397,8 @@ def test_bf16_trajectory_follows_exact_mode(golden):
     assert np.isfinite(he).all() and np.isfinite(hb).all()
     dev = np.abs(he - hb)
     cos = [_cos(a, b) for a, b in zip(runs[torch.float32][1], runs[torch.bfloat16][1])]
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/f14_trajectory.json", "w") as f:
-        json.dump({"max_abs_dev_per_term": dev.max(0).tolist(), "max_abs_dev_per_step": dev.max(1).tolist(),
-                   "displacement_cosine_G_Ds_Dt": cos, "exact_losses": he.tolist(), "bf16_losses": hb.tolist()}, f, indent=1)
+    _record("f14_trajectory.json", {"max_abs_dev_per_term": dev.max(0).tolist(), "max_abs_dev_per_step": dev.max(1).tolist(),
+                                    "displacement_cosine_G_Ds_Dt": cos, "exact_losses": he.tolist(), "bf16_losses": hb.tolist()})
     assert dev.max() < 2e-2, dev.max(0)
     assert dev.mean() < 4e-3, dev.mean(0)
     assert min(cos) > 0.99, cos

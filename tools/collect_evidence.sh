@@ -7,7 +7,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/ev_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $root
-timeout 500 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 500 python bench.py --full > $out/bench.json 2> $out/bench.err
 tail -c 1500 $out/bench.json
 # kernel durations with every kernel alone on the GPU (weight gradients on the launch stream): the per-kernel roofline table
 DVD_SIDE_SERIAL=1 timeout 500 rocprofv3 --kernel-trace --stats -d /tmp/prof_$tag -o st -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-prof > $out/prof.log 2>&1
@@ -17,8 +17,8 @@ tail -1 $out/prof.log | cut -c1-160
 timeout 500 rocprofv3 --kernel-trace --stats -d /tmp/profc_$tag -o st -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-prof > $out/prof_concurrent.log 2>&1
 python tools/rocpd_summary.py /tmp/profc_$tag/st_results.db $out/stats_concurrent.csv
 tail -1 $out/prof_concurrent.log | cut -c1-160
-DVD_PROF_CSV=/tmp/shapes_$tag.csv timeout 400 python bench.py --steps 1 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
-python tools/prof_shapes.py /tmp/shapes_$tag.csv 60 > $out/shapes.txt
+DVD_PROF_CSV=$TMPDIR/shapes_$tag.csv timeout 400 python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > /dev/null 2>&1
+python tools/prof_shapes.py $TMPDIR/shapes_$tag.csv 60 > $out/shapes.txt
 timeout 900 rocprofv3 -i tools/pmc_traffic.txt --kernel-trace -d /tmp/pmc_$tag -o pmc --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-kernel-prof > $out/pmc.log 2>&1
 python tools/traffic_summary.py /tmp/pmc_$tag $out/traffic.json "build $tag"
 python tools/stats_categories.py $out/stats.csv 3 > $out/categories.txt; cat $out/categories.txt
