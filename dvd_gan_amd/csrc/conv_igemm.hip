@@ -775,6 +775,7 @@ extern "C" int dvd_conv_forward_gru(const dvd_conv_desc* d, const GruEpi* g, voi
     const long long M = pl.M;
     const bool halo = pl.halo, thin = pl.thin, wide = pl.wide, big = pl.big;
     if (d->wq_kind >= 2 && !(d->wq_kind == 2 ? dvd_conv_thin_in_ok(d) : dvd_conv_thin_out_ok(d))) return DVD_E_ARG;   // a thin image the request cannot use
+    if (d->wq_kind >= 2 && d->pool2) return DVD_E_ARG;   // the thin kernels would write the full-size result into the half-size grid
     if (!g && d->wq && d->wq_kind == 2 && dvd_conv_thin_in_ok(d)) {      // the stems / the RGB layer's backward-data pass: taps folded into K (conv_thin.hip)
         ProfScope prof(0, 2.0 * (double)M * d->Cout * d->C * d->kt * d->kh * d->kw, stream, M, d->C, d->Cout, d->kt * d->kh * d->kw, 1,
                        d->relu_in << 1);

@@ -275,6 +275,7 @@ int dvd_conv_thin_in_ok(const dvd_conv_desc* d) {
     constexpr int use = 1;
     if (!use || !d || d->dtype != DVD_BF16 || d->C != 8 || d->ldi != 8 || d->Cout != 64 || d->ldo < 64 || (d->ldo & 7)) return 0;
     if (d->kh != 3 || d->kw != 3 || (d->kt != 1 && d->kt != 3) || d->up2 || d->res || d->ws || d->nsplit > 1) return 0;
+    if (d->pool2) return 0;                   // no 2 x 2 sum epilogue: a pool2 request goes to the halo-staged kernel
     if (d->act != DVD_ACT_NONE && d->act != DVD_ACT_RELU) return 0;
     if (d->W != 32 && d->W != 64) return 0;
     if (d->H % (PG / d->W) || d->frames < 1 || d->T < 1) return 0;
@@ -307,6 +308,7 @@ int dvd_conv_thin_out_ok(const dvd_conv_desc* d) {
     constexpr int use = 1;
     if (!use || !d || d->dtype != DVD_BF16 || d->C != 64 || d->ldi < 64 || (d->ldi & 7) || d->Cout < 1 || d->Cout > 8 || d->ldo < 8 || (d->ldo & 7)) return 0;
     if (d->kt != 1 || d->kh != 3 || d->kw != 3 || d->T != 1 || d->up2 || d->res || d->ws || d->nsplit > 1) return 0;
+    if (d->pool2) return 0;                   // (as dvd_conv_thin_in_ok)
     if (d->act != DVD_ACT_NONE && d->act != DVD_ACT_RELU && d->act != DVD_ACT_TANH) return 0;
     if (d->W != 32 && d->W != 64) return 0;
     if (d->H % (OG / d->W) || d->frames < 1) return 0;

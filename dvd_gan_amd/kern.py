@@ -232,6 +232,7 @@ def conv_forward(x, wpack, ksize, cout, *, bias=None, res=None, mask=None, act=L
     d.C, d.ldi, d.Cout = Cp, Cp, cout
     d.kt, d.kh, d.kw = k
     d.up2, d.relu_in, d.nsplit, d.act, d.out_f32 = int(up2), int(relu_in), nsplit, act, int(out_f32)
+    d.pool2 = int(pool2)                  # before the weight-image query: the thin kernels do not serve pool2 requests
     d.inp, d.w, d.bias = x.data_ptr(), wpack.data_ptr(), (bias.data_ptr() if bias is not None else None)
     if res is not None:
         d.res, d.ldres, d.res_up2 = res.data_ptr(), res.shape[-1], int(res_up2)
@@ -247,7 +248,6 @@ def conv_forward(x, wpack, ksize, cout, *, bias=None, res=None, mask=None, act=L
     d.wq = wq.data_ptr() if wq is not None else None
     d.out = d.ws = None
     if pool2:
-        d.pool2 = 1
         d.ldo = cout_pad or pad8(cout)
         if x.dim() != 4 or nsplit > 1 or slabs or ws is not None or not L.lib().dvd_conv_pool2_ok(C.byref(d)):
             return None

@@ -134,6 +134,27 @@ def test_dispatch_queries_need_no_gpu():
     assert ws(L.BF16, 64, 32, 32, 128, 3) == 65536 * 256      # unsplit: one slab of whole 256-column tiles
 
 
+@pytest.mark.parametrize("hw", [32, 64])
+@pytest.mark.parametrize("cin,cout,kind", [(8, 64, 2), (64, 8, 3)])
+def test_pool2_requests_skip_the_thin_kernels(cin, cout, kind, hw):
+    """A pool2 request (the 2 x 2 sums of an x2-upsampling conv's input gradient, written on the half-size grid) must not be handed
+    to the thin-input / thin-output kernels: they have no pool2 epilogue and would write a full-size result into the quarter-size
+    buffer.  It goes to the halo-staged kernel's epilogue instead; without pool2 the same geometry keeps its thin kernel.  Queries
+    only: dvd_conv_forward is never called with the placeholder pointers."""
+    from dvd_gan_amd import lib as L
+    lib = L.lib()
+    d = L.ConvDesc()
+    d.dtype, d.frames, d.T, d.H, d.W = L.BF16, 2, 1, hw, hw
+    d.C, d.ldi, d.Cout, d.ldo = cin, cin, cout, cout
+    d.kt, d.kh, d.kw, d.nsplit = 1, 3, 3, 1
+    d.inp = d.out = d.w = 1                          # never dereferenced by the queries
+    assert lib.dvd_conv_wants_fragment_major(ctypes.byref(d)) == kind
+    assert lib.dvd_conv_pool2_ok(ctypes.byref(d)) == 0
+    d.pool2 = 1
+    assert lib.dvd_conv_pool2_ok(ctypes.byref(d)) == 1
+    assert lib.dvd_conv_wants_fragment_major(ctypes.byref(d)) == 1
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from dvd_gan_amd import lib as L
     monkeypatch.setattr(L, "_lib", None)

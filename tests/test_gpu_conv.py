@@ -102,6 +102,9 @@ CASES = [
     (5, 40, 264, (6, 6), (5, 5), False, False),          # wide N, ragged M
     (1, 8, 16, (3, 6, 6), (3, 3, 3), False, False),      # 3-D
     (2, 24, 72, (48, 48), (3, 3), False, False),         # a multiple of 16 that is not a power of two
+    # x2-upsampling layers whose backward-data pass has a thin geometry: its pool2 request must go to the halo-staged kernel
+    (2, 64, 8, (16, 16), (3, 3), True, True),            # 8 -> 64 on 32 x 32 (the thin-input kernel's shape)
+    (2, 8, 64, (32, 32), (3, 3), True, False),           # 64 -> 8 on 64 x 64 (the thin-output kernel's shape)
 ]
 
 
