@@ -202,43 +202,62 @@ __global__ __launch_bounds__(256) void attn_bwd_rows_kernel(const T* kv, int ldk
 }
 
 // Backward, column pass: dv[j][c] = gamma * sum_i A[i][j] dy[i][c];  dk[j][d] = sum_i dS[i][j] q[i][d]
+// The query axis is walked in chunks of NR rows (NR = N when [N][QB] fits 64 KB of LDS: one chunk, staged once); every sum
+// still runs over i = 0 .. N - 1 in order, so the chunking changes no result bit.  (The first form staged all N rows and
+// refused N > 2048, which the forward accepts: the generator's 3-D attention at 128 x 128 has N = 3072.)
 template <typename T, int QB>
 __global__ __launch_bounds__(256) void attn_bwd_cols_kernel(const T* qkv, int ldq, int dq, int koff, int voff, const T* dy,
                                                             int ldx, int C, const float* gamma, const float* A,
-                                                            const float* dS, T* dkv, int ldk, int N, int Nk) {
-    extern __shared__ float S[];                   // [N][QB] slice of A, then of dS (column block j0..j0+QB)
+                                                            const float* dS, T* dkv, int ldk, int N, int Nk, int NR) {
+    extern __shared__ float S[];                   // [NR][QB] slice of A, then of dS (column block j0..j0+QB, rows i0..i0+NR)
     const int f = blockIdx.y, j0 = blockIdx.x * QB, tid = threadIdx.x;
     const T* qf = qkv + (size_t)f * N * ldq;
     const float g = *gamma;
-    for (int idx = tid; idx < N * QB; idx += 256) {
-        const int i = idx / QB, jj = idx - i * QB;
-        S[idx] = (j0 + jj < Nk) ? A[((size_t)f * N + i) * Nk + j0 + jj] : 0.f;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < (QB / 4) * C; idx += 256) {
-        const int jb = (idx / C) * 4, c = idx % C;
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int i = 0; i < N; ++i) {
-            const float d = ldf(dy + ((size_t)f * N + i) * ldx + c);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[r] += S[i * QB + jb + r] * d;
+    int staged = -1;                               // first row of the chunk in S (block-uniform)
+    auto stage = [&](const float* src, int i0) __attribute__((always_inline)) {
+        if (staged == i0) return;
+        const int nr = min(NR, N - i0);
+        __syncthreads();
+        for (int idx = tid; idx < nr * QB; idx += 256) {
+            const int i = idx / QB, jj = idx - i * QB;
+            S[idx] = (j0 + jj < Nk) ? src[((size_t)f * N + i0 + i) * Nk + j0 + jj] : 0.f;
         }
+        __syncthreads();
+        staged = i0;
+    };
+    for (int base = 0; base < (QB / 4) * C; base += 256) {     // block-uniform trip count: every thread meets every barrier
+        const int idx = base + tid;
+        const bool live = idx < (QB / 4) * C;
+        const int jb = live ? (idx / C) * 4 : 0, c = live ? idx % C : 0;
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int i0 = 0; i0 < N; i0 += NR) {
+            stage(A, i0);
+            if (!live) continue;
+            const int nr = min(NR, N - i0);
+            for (int i = 0; i < nr; ++i) {
+                const float d = ldf(dy + ((size_t)f * N + i0 + i) * ldx + c);
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (j0 + jb + r < Nk) stf(dkv + ((size_t)f * Nk + j0 + jb + r) * ldk + voff + c, g * acc[r]);
+                for (int r = 0; r < 4; ++r) acc[r] += S[i * QB + jb + r] * d;
+            }
+        }
+        if (live)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (j0 + jb + r < Nk) stf(dkv + ((size_t)f * Nk + j0 + jb + r) * ldk + voff + c, g * acc[r]);
     }
-    __syncthreads();
-    for (int idx = tid; idx < N * QB; idx += 256) {
-        const int i = idx / QB, jj = idx - i * QB;
-        S[idx] = (j0 + jj < Nk) ? dS[((size_t)f * N + i) * Nk + j0 + jj] : 0.f;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < QB * dq; idx += 256) {
+    staged = -1;
+    for (int base = 0; base < QB * dq; base += 256) {
+        const int idx = base + tid;
         const int jj = idx / dq, d = idx - jj * dq;
-        if (j0 + jj >= Nk) continue;
+        const bool live = idx < QB * dq && j0 + jj < Nk;
         float s = 0.f;
-        for (int i = 0; i < N; ++i) s += S[i * QB + jj] * ldf(qf + (size_t)i * ldq + d);
-        stf(dkv + ((size_t)f * Nk + j0 + jj) * ldk + koff + d, s);
+        for (int i0 = 0; i0 < N; i0 += NR) {
+            stage(dS, i0);
+            if (!live) continue;
+            const int nr = min(NR, N - i0);
+            for (int i = 0; i < nr; ++i) s += S[i * QB + jj] * ldf(qf + (size_t)(i0 + i) * ldq + d);
+        }
+        if (live) stf(dkv + ((size_t)f * Nk + j0 + jj) * ldk + koff + d, s);
     }
 }
 
@@ -305,15 +324,16 @@ static int attention_bwd(int dtype, const void* q, int ldq, int dq, const void* 
     if (!q || !kv || !dy || !gamma || !att_out || !A || !dS || !dqo || !dkv || frames <= 0 || N <= 0 || Nk <= 0) return DVD_E_ARG;
     if (frames > 65535 || (C & 7)) return DVD_E_SHAPE;
     const int qb = ((size_t)16 * (Nk + C) * sizeof(float) <= 64 * 1024 && (size_t)16 * N * sizeof(float) <= 64 * 1024) ? 16 : 8;
-    if ((size_t)qb * (Nk + C) * sizeof(float) > 64 * 1024 || (size_t)qb * N * sizeof(float) > 64 * 1024) return DVD_E_SHAPE;
+    if ((size_t)qb * (Nk + C) * sizeof(float) > 64 * 1024) return DVD_E_SHAPE;
+    const int nr = (int)std::min<size_t>((size_t)N, 64 * 1024 / (qb * sizeof(float)));      // query rows per column-pass chunk
     dim3 grid_r(cdiv(N, qb), (unsigned)frames), grid_c(cdiv(Nk, qb), (unsigned)frames);
-    const size_t sh_rows = (size_t)qb * (Nk + C) * sizeof(float), sh_cols = (size_t)qb * N * sizeof(float);
+    const size_t sh_rows = (size_t)qb * (Nk + C) * sizeof(float), sh_cols = (size_t)qb * nr * sizeof(float);
 #define ATT_BWD(QB_)                                                                                                    \
     do {                                                                                                                \
         BY_DTYPE(dtype, attn_bwd_rows_kernel<T, QB_><<<grid_r, 256, sh_rows, S_>>>((const T*)kv, ldk, dq, koff, voff,   \
                             (const T*)dy, ldx, C, gamma, (const T*)att_out, A, dS, (T*)dqo, ldq, dgamma, N, Nk));       \
         BY_DTYPE(dtype, attn_bwd_cols_kernel<T, QB_><<<grid_c, 256, sh_cols, S_>>>((const T*)q, ldq, dq, koff, voff,    \
-                            (const T*)dy, ldx, C, gamma, A, dS, (T*)dkv, ldk, N, Nk));                                  \
+                            (const T*)dy, ldx, C, gamma, A, dS, (T*)dkv, ldk, N, Nk, nr));                                  \
     } while (0)
     if (qb == 16) ATT_BWD(16); else ATT_BWD(8);
 #undef ATT_BWD

@@ -119,6 +119,8 @@ def test_dispatch_queries_need_no_gpu():
     assert ok(L.BF16, 160, 16, 16, 32, 128, 128, 256) == 1 and ok(L.BF16, 160, 16, 16, 32, 128, 128, 1024) == 1
     assert ok(L.F32, 160, 16, 16, 32, 128, 128, 256) == 0 and ok(L.BF16, 80, 8, 8, 16, 64, 64, 256) == 0
     assert ok(L.BF16, 160, 16, 16, 32, 128, 128, 48) == 0     # not whole 32-token blocks
+    assert ok(L.BF16, 160, 16, 16, 32, 128, 128, 32) == 1 and ok(L.BF16, 160, 16, 16, 32, 128, 128, 4096) == 1
+    assert ok(L.BF16, 160, 16, 16, 32, 128, 128, 4128) == 0   # past the 4096-token limit
     w = L.WgradDesc()
     w.dtype, w.frames, w.T, w.H, w.W = L.BF16, 64, 12, 32, 32
     w.C, w.ldx, w.Cin_real, w.Cout, w.Cy, w.ldy = 8, 8, 3, 64, 64, 64
@@ -153,6 +155,32 @@ def test_pool2_requests_skip_the_thin_kernels(cin, cout, kind, hw):
     d.pool2 = 1
     assert lib.dvd_conv_pool2_ok(ctypes.byref(d)) == 1
     assert lib.dvd_conv_wants_fragment_major(ctypes.byref(d)) == 1
+
+
+def test_attention_refusal_rules_need_no_gpu():
+    """The shapes the attention entry points refuse before any launch (DVD_E_SHAPE): the MFMA kernels past 4096 tokens, the
+    separable cell past an attended size of 64, the fp32 kernels' LDS limits -- forward [QB][Nk] scores + queries + partial
+    outputs, backward [QB][Nk + C].  The fp32 backward walks the query axis in chunks, so N itself has no limit there (the
+    generator's 3-D attention at 128 x 128 has N = 3072: tests/test_gpu_attention.py runs it).  Every call below is refused by
+    its host-side checks; the placeholder pointers are never dereferenced and nothing is launched."""
+    from dvd_gan_amd import lib as L
+    lib = L.lib()
+    p = ctypes.c_void_p(1)
+    one = ctypes.c_longlong(1)
+    assert lib.dvd_attention_mfma_ok(L.BF16, 160, 16, 16, 32, 128, 128, 4128) == 0
+    assert lib.dvd_attention_mfma_forward(p, 160, p, 128, p, p, p, p, one, 4128, None) == -2
+    assert lib.dvd_attention_mfma_backward(p, 160, p, 128, p, p, p, p, p, p, one, 4128, None) == -2
+    # sepattn: A = W = 66 > 64 (the 64 x 32 product tiles)
+    assert lib.dvd_sepattn_work_floats(8, 66, 8, 1, 64, 32) == 0 and lib.dvd_sepattn_work_floats(8, 64, 8, 1, 64, 32) > 0
+    assert lib.dvd_sepattn_forward(L.BF16, p, 128, 32, 32, 64, p, 64, 64, p, p, p, p, p, p, p, p, one, 8, 66, 8, 1, None) == -2
+    assert lib.dvd_sepattn_backward(L.BF16, p, 64, 64, 32, p, p, p, p, p, p, p, p, p, p, p, p, p, 128, 32, 64, p, one,
+                                    8, 8, 66, 2, None) == -2
+    # fp32 forward at dq = 8, C = 64: 8 N + 8 dqp + 32 C floats of LDS -> N = 1784 is the largest (the GPU suite runs it)
+    assert lib.dvd_attention_forward(L.F32, p, 80, 8, 8, 16, p, 64, 64, p, p, p, p, one, 1785, None) == -2
+    # fp32 backward: [8][Nk + C] floats past 64 KB (Nk = 1800, C = 256); the forward of the same call is refused as well
+    assert lib.dvd_attention_kv_backward(L.F32, p, 8, 8, p, 512, 8, 16, p, 256, 256, p, p, p, p, p, p, p, one, 64, 1800,
+                                         None) == -2
+    assert lib.dvd_attention_backward(L.BF16, p, 2072, 8, 8, 16, p, 2056, 2056, p, p, p, p, p, p, one, 8, None) == -2
 
 
 def test_missing_library_fails_loudly(monkeypatch):

@@ -45,7 +45,7 @@ def check_bound(out, ref, bound32, dtype, name):
     """|out - ref| <= bound32 + half an ulp of the storage dtype at ref, elementwise; returns the worst err / allowed."""
     err = (out.double() - ref).abs()
     allowed = bound32 + half_ulp(ref, dtype)
-    bad = err > allowed
+    bad = ~(err <= allowed)                                  # (a NaN or inf in `out` is outside every bound)
     ratio = float((err / allowed.clamp_min(1e-300)).max()) if err.numel() else 0.0
     assert not bool(bad.any()), f"{name}: {int(bad.sum())} elements outside the bound (worst err / allowed {ratio:.3g})"
     return ratio
