@@ -521,6 +521,34 @@ __global__ void vid_down_kernel(const float* src, float* dst, int B, int T, int 
         dst[i] = 0.25f * src[((((size_t)b * C + c) * T + t) * Ho + y / 2) * Wo + x / 2];
     }
 }
+// vid_downsample of the time concatenation [a | b] (a: [B][Ta][C][H][W], b: [B][Tb][C][H][W]) without materialising it:
+// forward dst [B][C][Ta+Tb][Ho][Wo] with vid_down_kernel's per-element arithmetic; backward writes d(b) only (into b) from
+// d(dst) (in dst): the frames of `a` are data
+__global__ void vid_down_cat_kernel(const float* a, int Ta, float* b, int Tb, float* dst, int B, int C, int H, int W, int bwd) {
+    const int Ho = H / 2, Wo = W / 2, T = Ta + Tb;
+    const long long n = bwd ? (long long)B * Tb * C * H * W : (long long)B * C * T * Ho * Wo;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!bwd) {
+        long long r = i;
+        const int x = (int)(r % Wo); r /= Wo;
+        const int y = (int)(r % Ho); r /= Ho;
+        const int t = (int)(r % T); r /= T;
+        const int c = (int)(r % C);
+        const int bb = (int)(r / C);
+        const float* s = t < Ta ? a + ((((size_t)bb * Ta + t) * C + c) * H + 2 * y) * W + 2 * x
+                                : b + ((((size_t)bb * Tb + (t - Ta)) * C + c) * H + 2 * y) * W + 2 * x;
+        dst[i] = (s[0] + s[1] + s[W] + s[W + 1]) * 0.25f;
+    } else {
+        long long r = i;
+        const int x = (int)(r % W); r /= W;
+        const int y = (int)(r % H); r /= H;
+        const int c = (int)(r % C); r /= C;
+        const int t = (int)(r % Tb);
+        const int bb = (int)(r / Tb);
+        b[i] = 0.25f * dst[((((size_t)bb * C + c) * T + Ta + t) * Ho + y / 2) * Wo + x / 2];
+    }
+}
 // dst row r = src row idx[r] (gather) or dst row idx[r] = src row r (scatter); rows of L floats
 __global__ void row_copy_kernel(const float* src, float* dst, const int* idx, long long nrows, long long L, int scatter) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -712,6 +740,14 @@ extern "C" int dvd_vid_downsample(const float* src, float* dst, int B, int T, in
     if ((H | W) & 1) return DVD_E_SHAPE;
     const long long n = backward ? (long long)B * T * C * H * W : (long long)B * C * T * (H / 2) * (W / 2);
     vid_down_kernel<<<cdiv(n, 256), 256, 0, S_>>>(src, dst, B, T, C, H, W, backward);
+    return launch_status();
+}
+extern "C" int dvd_vid_downsample_cat(const float* a, int Ta, float* b, int Tb, float* dst, int B, int C, int H, int W,
+                                      int backward, void* stream) {
+    if ((!backward && !a) || !b || !dst || Ta <= 0 || Tb <= 0 || B <= 0 || C <= 0 || H <= 0 || W <= 0) return DVD_E_ARG;
+    if ((H | W) & 1) return DVD_E_SHAPE;
+    const long long n = backward ? (long long)B * Tb * C * H * W : (long long)B * C * (Ta + Tb) * (H / 2) * (W / 2);
+    vid_down_cat_kernel<<<cdiv(n, 256), 256, 0, S_>>>(a, Ta, b, Tb, dst, B, C, H, W, backward);
     return launch_status();
 }
 extern "C" int dvd_row_copy(const float* src, float* dst, const int* idx, long long nrows, long long L, int scatter,

@@ -961,6 +961,24 @@ class VidDownsample(Function):
         return K.vid_downsample_raw(g.contiguous(), True, ctx.shape)
 
 
+class VidDownsampleCat(Function):
+    """utils.py:77-83 of torch.cat([context, x], 1) in one pass (dvd_vid_downsample_cat): D_t's input of the frame-conditional
+    variant.  The context frames are data: only x receives a gradient."""
+
+    @staticmethod
+    def forward(ctx, context, x):
+        if ctx.needs_input_grad[0]:
+            raise ValueError("VidDownsampleCat: the context frames receive no gradient (detach them)")
+        if context.shape[0] != x.shape[0] or context.shape[2:] != x.shape[2:]:
+            raise ValueError(f"VidDownsampleCat: context {tuple(context.shape)} and clip {tuple(x.shape)} differ outside the time axis")
+        ctx.Ta, ctx.shape = context.shape[1], tuple(x.shape)
+        return K.vid_downsample_cat_raw(context.contiguous(), x.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, K.vid_downsample_cat_backward(g.contiguous(), ctx.Ta, ctx.shape)
+
+
 def _ids_to(ids, device):
     from .helpers import to_device_async
     return to_device_async(ids, device)

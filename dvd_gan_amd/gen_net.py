@@ -108,7 +108,7 @@ class Generator(nn.Module):
     .forward(z [B,in_dim] f32, class_id [B] i64) -> [B, T, 3, 16*latent_dim, 16*latent_dim] f32."""
 
     def __init__(self, in_dim=120, latent_dim=4, n_class=4, ch=32, n_frames=48, hierar_flag=False,
-                 compute_dtype=torch.bfloat16, self_attn=False, sep_attn=False):
+                 compute_dtype=torch.bfloat16, self_attn=False, sep_attn=False, n_cond=0):
         """self_attn / sep_attn switch on the two attention blocks the reference defines and imports (Generator.py:10) but
         leaves commented out: `self.self_attn = SelfAttention(8 * ch)` (:29) over the (T, ld, ld) latent clip after the first
         ConvGRU, and `SeparableAttn(4 * ch)` (:34, after the block that produces 4*ch channels) over the (T, 8 ld, 8 ld) clip
@@ -121,6 +121,8 @@ class Generator(nn.Module):
                              "hidden size 4*ch must be a multiple of 8 (ch even)")
         if latent_dim < 1:
             raise ValueError(f"latent_dim={latent_dim}")
+        if n_cond < 0:
+            raise ValueError(f"n_cond={n_cond}")
         # (power-of-two latent_dim -- 4 -> 64x64, 8 -> 128x128 clips -- runs the LDS-staged kernels; any other value, e.g. 3 or 6
         #  -> 48x48 / 96x96, the tap-by-tap kernels with division indexing: same results, lower throughput)
         self.in_dim, self.latent_dim, self.n_class, self.ch, self.n_frames = in_dim, latent_dim, n_class, ch, n_frames
@@ -147,21 +149,38 @@ class Generator(nn.Module):
                 self.self_attn = SelfAttention(c8, compute_dtype)
             if sep_attn:
                 self.sep_attn = SeparableAttn(c4, compute_dtype)
+        self.n_cond = n_cond
+        if n_cond:
+            from .cond_encoder import FrameEncoder
+            self.cond_encoder = FrameEncoder(n_cond, latent_dim, ch, compute_dtype)
         self.dp_global = False                      # data-parallel "global" mode: conditions gathered over the ranks
         self.dp_hooks = False                       # data-parallel trainer sets it: stage-boundary gradient hooks
         self.grad_ready_hook = None                 # callable(first finished module index), armed around backward
         self.grad_ready_stages = (2, 5, 8)          # after each [ConvGRU, GResBlock, GResBlock] group but the last
 
-    def forward(self, x, class_id, hidden=None):
-        """hidden (frame-conditional variant, BASELINE configs[4]): initial ConvGRU states carried in from a conditioning
-        encoder -- one entry per ConvGRU of the stack (4), each None or a list of that ConvGRU's per-layer states
-        [B, hidden_l, S, S] fp32 (None entries = zeros).  They take the place of the `hidden=None` the reference passes at
-        the first frame (Generator.py:91,96 -> ConvGRU.forward(x, hidden), ConvGRU.py:104-118) and receive gradients."""
+    def forward(self, x, class_id, hidden=None, cond=None):
+        """hidden (frame-conditional variant, BASELINE configs[4]): initial ConvGRU states supplied by the caller -- one entry
+        per ConvGRU of the stack (4), each None or a list of that ConvGRU's per-layer states [B, hidden_l, S, S] fp32 (None
+        entries = zeros).  They take the place of the `hidden=None` the reference passes at the first frame (Generator.py:91,96
+        -> ConvGRU.forward(x, hidden), ConvGRU.py:104-118) and receive gradients.
+        cond (n_cond > 0, and then required): the context frames [B, n_cond, 3, 16 ld, 16 ld] fp32 in [-1, 1], the layout of this
+        generator's own output; the conditioning encoder turns them into the initial states (exclusive with `hidden`)."""
+        if self.n_cond:
+            if hidden is not None:
+                raise ValueError("a conditional generator (n_cond > 0) takes its initial states from `cond`, not `hidden`")
+            if cond is None:
+                raise ValueError(f"a conditional generator (n_cond={self.n_cond}) needs the context frames `cond`")
+            self.cond_encoder.check(cond, x.shape[0])
+        elif cond is not None:
+            raise ValueError("`cond` needs a generator built with n_cond > 0")
         sn = prefetch_spectral_norm(self, self.compute_dtype)    # SN + weight packing of all layers on the side stream
         counted = self._count_batches() if self.training else []
         for m in counted:
             m.count_batches = False
         try:
+            if cond is not None:
+                # channels-last states in the compute dtype, read by the ConvGRUs as they are
+                return self._forward(x, class_id, self.cond_encoder(cond), states_cl=True)
             return self._forward(x, class_id, hidden)
         finally:
             for m in counted:                     # (only modules that were counting are switched back on)
@@ -180,7 +199,7 @@ class Generator(nn.Module):
             torch._foreach_add_([m.bn.num_batches_tracked for m in mods], 1)
         return mods
 
-    def _forward(self, x, class_id, hidden=None):
+    def _forward(self, x, class_id, hidden=None, states_cl=False):
         B, T = x.shape[0], self.n_frames
         dev = x.device
         class_emb = Fn.Embedding.apply(self.embedding.weight, class_id.to(torch.int32))
@@ -204,7 +223,7 @@ class Generator(nn.Module):
             if isinstance(m, ConvGRU):
                 h0 = hidden[n_gru] if hidden is not None else None
                 n_gru += 1
-                if h0 is not None:
+                if h0 is not None and not states_cl:
                     if len(h0) != m.n_layers:
                         raise ValueError("`hidden` needs one state (or None) per ConvGRU layer")
                     h0 = [None if h is None else Fn.ToChannelsLast.apply(h, self.compute_dtype, None) for h in h0]

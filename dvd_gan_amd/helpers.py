@@ -36,6 +36,12 @@ def vid_downsample(data):
     return Fn.VidDownsample.apply(data)
 
 
+def vid_downsample_cat(context, data):
+    """vid_downsample(torch.cat([context, data], 1)) without the concatenated clip: [B,Tc,C,H,W] + [B,T,C,H,W] ->
+    [B,C,Tc+T,H/2,W/2]; the gradient reaches `data` only (the context frames are data)."""
+    return Fn.VidDownsampleCat.apply(context, data)
+
+
 def denorm(x):
     """utils.py:41-43: [-1, 1] -> [0, 1], clamped."""
     return ((x + 1) / 2).clamp_(0, 1)

@@ -464,6 +464,24 @@ def vid_downsample_raw(src, backward, shape_fwd_in):
     return out
 
 
+def vid_downsample_cat_raw(a, b):
+    """vid_downsample(cat([a, b], 1)) of two fp32 clips [B, Ta, C, H, W] / [B, Tb, C, H, W] -> [B, C, Ta+Tb, H/2, W/2]."""
+    B, Ta, Cc, H, W = a.shape
+    Tb = b.shape[1]
+    out = torch.empty(B, Cc, Ta + Tb, H // 2, W // 2, dtype=torch.float32, device=b.device)
+    L.check(L.lib().dvd_vid_downsample_cat(L.ptr(a), Ta, L.ptr(b), Tb, L.ptr(out), B, Cc, H, W, 0, L.stream()))
+    return out
+
+
+def vid_downsample_cat_backward(g, Ta, shape_b, db=None):
+    """Gradient of vid_downsample_cat_raw wrt b from g [B, C, Ta+Tb, H/2, W/2] (the context frames get none)."""
+    B, Tb, Cc, H, W = shape_b
+    if db is None:
+        db = torch.empty(shape_b, dtype=torch.float32, device=g.device)
+    L.check(L.lib().dvd_vid_downsample_cat(None, Ta, L.ptr(db), Tb, L.ptr(g), B, Cc, H, W, 1, L.stream()))
+    return db
+
+
 def row_copy(src, idx, nrows_out, L_, scatter, out=None):
     """gather: out[r] = src[idx[r]] ; scatter: out[idx[r]] = src[r] (out pre-zeroed, nrows_out rows)."""
     if out is None:

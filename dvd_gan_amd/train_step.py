@@ -6,6 +6,9 @@
     D_s(real) , D_s(fake.detach)  -> backward -> ds Adam
     D_t(real↓), D_t(fake↓.detach) -> backward -> dt Adam
     D_s(fake), D_t(fake↓) on the UPDATED discriminators -> relu(1 - out) -> backward -> g Adam
+Frame-conditional video prediction (config.n_cond = K > 0, BASELINE configs[4]): the clips are K context frames followed by
+n_frames targets; the generator encodes the context (cond_encoder.FrameEncoder), D_s judges target frames against generated
+ones, D_t judges whole clips -- the real clip against [context | generated].
 Differences that do not change results: the dead D weight-gradients of the generator step are not
 computed; Adam is one fused launch per network; gradients are exchanged with RCCL (dist.py).
 Out of scope: tensorboard logging, sample grids, dataset loaders.
@@ -21,7 +24,7 @@ from . import dist as D
 from .dist import GradExchange
 from .disc_nets import SpatialDiscriminator, TemporalDiscriminator
 from .gen_net import Generator
-from .helpers import denorm, draw_frame_ids, sample_k_frames, to_device_async, vid_downsample
+from .helpers import denorm, draw_frame_ids, sample_k_frames, to_device_async, vid_downsample, vid_downsample_cat
 from .optim import FlatAdam
 
 
@@ -103,6 +106,13 @@ class Trainer(object):
         self.total_epoch, self.d_iters, self.batch_size = c.total_epoch, c.d_iters, c.batch_size
         self.g_lr, self.d_lr, self.beta1, self.beta2 = c.g_lr, c.d_lr, c.beta1, c.beta2
         self.n_class, self.k_sample = c.n_class, c.k_sample
+        self.n_cond = int(getattr(c, "n_cond", 0))
+        if self.n_cond < 0:
+            raise ValueError(f"n_cond={self.n_cond}")
+        if self.n_cond and (self.n_cond + self.n_frames) % 4:
+            # D_t sees context + generated frames and pools time twice (TemporalDiscriminator._forward)
+            raise ValueError(f"n_cond + n_frames = {self.n_cond + self.n_frames} must be a multiple of 4: D_t judges the context "
+                             "and the generated frames together and pools time twice")
         self.lr_decay = getattr(c, "lr_decay", 0.9999)
         self.pretrained_model = getattr(c, "pretrained_model", None)
         self.model_save_path = os.path.join(getattr(c, "model_save_path", "./models"), getattr(c, "version", ""))
@@ -151,7 +161,8 @@ class Trainer(object):
         dt = self.compute_dtype
         c = self.config
         self.G = Generator(self.z_dim, self.latent_dim, self.n_class, self.g_chn, self.n_frames, compute_dtype=dt,
-                           self_attn=getattr(c, "g_self_attn", False), sep_attn=getattr(c, "g_sep_attn", False)).to(self.device)
+                           self_attn=getattr(c, "g_self_attn", False), sep_attn=getattr(c, "g_sep_attn", False),
+                           n_cond=self.n_cond).to(self.device)
         self.D_s = SpatialDiscriminator(self.ds_chn, self.n_class, compute_dtype=dt).to(self.device)
         self.D_t = TemporalDiscriminator(self.dt_chn, self.n_class, compute_dtype=dt).to(self.device)
         if self.exchange.active and self.dp_mode == "global":
@@ -170,9 +181,11 @@ class Trainer(object):
     def select_opt_schr(self):
         betas = (self.beta1, self.beta2)
         self.g_optimizer = FlatAdam(self.G.parameters(), self.g_lr, betas)
-        # (the optional attention blocks sit at the END of the parameter order but finish their gradients late in the
-        #  backward pass: with them the generator's gradient goes in one piece)
-        self.G.dp_hooks = self.exchange.active and os.environ.get("DVD_DP_HOOKS", "1") != "0" and not (hasattr(self.G, "self_attn") or hasattr(self.G, "sep_attn"))
+        # (the optional attention blocks and the conditioning encoder sit at the END of the parameter order but finish their
+        #  gradients late in the backward pass -- the encoder's last of all, behind the dh0 of the first ConvGRU: with them the
+        #  generator's gradient goes in one piece)
+        self.G.dp_hooks = self.exchange.active and os.environ.get("DVD_DP_HOOKS", "1") != "0" and not (
+            hasattr(self.G, "self_attn") or hasattr(self.G, "sep_attn") or hasattr(self.G, "cond_encoder"))
         # offset of the first trainable parameter of generator module conv.k in the flat buffers (gradient buckets)
         self._g_bounds, off = {}, 0
         for name, prm in self.G.named_parameters():
@@ -236,11 +249,20 @@ class Trainer(object):
     def train_step(self, real_videos, real_labels, draws=None, hidden=None):
         """real_videos [B,3,T,H,W], real_labels [B].  `draws` (tests): dict with the reference's RNG
         draws perm_real / z / z_class / perm_fake.  `hidden`: initial ConvGRU states for the generator
-        (Generator.forward, frame-conditional variant).  Returns the six loss terms as device scalars:
+        (Generator.forward, frame-conditional variant).  With n_cond = K > 0 the clips are [B,3,K+T,H,W]: the first K frames
+        condition the generator (`hidden` is then an error), perm_real / perm_fake draw over the T target frames, D_t sees
+        all K+T frames.  Returns the six loss terms as device scalars:
         ds_real, ds_fake, dt_real, dt_fake, g_s, g_t.
         The step's dependent chain runs on a HIGH-priority stream so its (often small) launches are dispatched ahead of
         the bulk weight-gradient work queued on the normal-priority side stream; the caller's stream is ordered before
         and after the step, so nothing changes for it."""
+        if self.n_cond:
+            if hidden is not None:
+                raise ValueError("a frame-conditional Trainer (n_cond > 0) takes its generator states from the context frames, "
+                                 "not from `hidden`")
+            if real_videos.dim() != 5 or real_videos.shape[2] != self.n_cond + self.n_frames:
+                raise ValueError(f"clips must be [B, 3, n_cond + n_frames = {self.n_cond + self.n_frames}, H, W], got "
+                                 f"{tuple(real_videos.shape)}")
         if self._chain is None:
             return self._train_step(real_videos, real_labels, draws, hidden)
         outer = torch.cuda.current_stream()
@@ -256,7 +278,8 @@ class Trainer(object):
         L.reset_gru_tickets(current_stream_only=True)         # split-K tickets start every step from zero (lib.reset_gru_tickets)
         real_videos = to_device_async(real_videos, self.device).permute(0, 2, 1, 3, 4).contiguous()
         real_labels = to_device_async(self._check_labels(real_labels), self.device)
-        T, k = self.n_frames, self.k_sample
+        T, k, Kc = self.n_frames, self.k_sample, self.n_cond
+        cond = real_videos[:, :Kc].contiguous() if Kc else None       # [B,K,3,H,W] context frames; the targets follow them
         ex = self.exchange
         fg = self.frame_gen
         draws_all = draws
@@ -264,7 +287,7 @@ class Trainer(object):
             if isinstance(draws_all, (list, tuple)):              # test aid: one dict of draws per discriminator iteration
                 draws = draws_all[_]
             ids_real = draw_frame_ids(T, k, fg) if draws is None else torch.as_tensor(draws["perm_real"])[:k].sort()[0]
-            real_s = sample_k_frames(real_videos, T, k, ids_real)
+            real_s = sample_k_frames(real_videos, T + Kc, k, ids_real + Kc if Kc else ids_real)
             z = to_device_async(torch.randn(self.batch_size, self.z_dim, generator=self.noise_gen) if draws is None
                                 else torch.as_tensor(draws["z"]), self.device)
             z_class = self.label_sample() if draws is None else to_device_async(self._check_labels(torch.as_tensor(draws["z_class"])), self.device)
@@ -283,7 +306,7 @@ class Trainer(object):
                     dt_loss_real = self.calc_loss(self.D_t(real_d, real_labels), True)
                 for t_ in (real_s, real_videos, real_labels):
                     t_.record_stream(self._aux)
-            fake_videos = self.G(z, z_class, hidden)
+            fake_videos = self.G(z, z_class, hidden, cond=cond)
             ids_fake = draw_frame_ids(T, k, fg) if draws is None else torch.as_tensor(draws["perm_fake"])[:k].sort()[0]
             fake_s = sample_k_frames(fake_videos, T, k, ids_fake)
             # ---------------- D_s
@@ -299,7 +322,7 @@ class Trainer(object):
             Fn.join_side()
             ex.start("Ds", self.ds_optimizer.grad)
             # ---------------- D_t (its forward/backward overlaps the D_s gradient exchange)
-            fake_d = vid_downsample(fake_videos)
+            fake_d = vid_downsample(fake_videos) if cond is None else vid_downsample_cat(cond, fake_videos)
             if not early:
                 real_d = vid_downsample(real_videos)
                 dt_loss_real = self.calc_loss(self.D_t(real_d, real_labels), True)
@@ -388,9 +411,28 @@ class Trainer(object):
     def sample(self, fixed_z, fixed_label):
         """-> denorm(G(fixed_z, fixed_label)) [B, T, 3, H, W] in [0, 1]; G is put back in train mode, like the reference.
         Note quirk 2: the spectral-norm u/v of G advance in eval mode as well."""
+        if self.n_cond:
+            raise RuntimeError("a frame-conditional generator (n_cond > 0) continues clips: use Trainer.predict(cond, labels)")
         self.G.eval()
         fake = self.G(fixed_z.to(self.device), fixed_label.to(self.device))
         self.G.train()
+        return denorm(fake)
+
+    @torch.no_grad()
+    def predict(self, cond, labels, z=None):
+        """Frame-conditional prediction (n_cond = K > 0): cond [B, K, 3, H, W] context frames in [-1, 1] (the generator's output
+        layout, so denormalised predictions come back in as 2 p - 1), labels [B] -> denorm(G(z, labels, cond=cond)), the next
+        n_frames frames [B, T, 3, H, W] in [0, 1].  z [B, z_dim] defaults to a fresh draw.  Eval / train mode as in sample()."""
+        if not self.n_cond:
+            raise RuntimeError("predict() needs a frame-conditional Trainer (config.n_cond > 0); use sample()")
+        B = cond.shape[0]
+        if z is None:
+            z = torch.randn(B, self.z_dim, generator=self.noise_gen)
+        self.G.eval()
+        try:
+            fake = self.G(z.to(self.device), self._check_labels(labels).to(self.device), cond=cond.to(self.device, torch.float32))
+        finally:
+            self.G.train()
         return denorm(fake)
 
     # ---- trainer.py:337-343 / 375-382: reference-compatible checkpoints

@@ -347,6 +347,12 @@ int dvd_act_backward(int dtype, const void* dy, const void* y, void* dx, long lo
 /* utils.py:77-83 vid_downsample on reference-layout fp32 tensors (+ its backward) and
  * utils.py:60-63 frame gather: rows of L floats copied by index (scatter = transpose). */
 int dvd_vid_downsample(const float* src, float* dst, int B, int T, int C, int H, int W, int backward, void* stream);
+/* utils.py:77-83 vid_downsample of torch.cat([a, b], 1) without the concatenated clip (D_t's input of the frame-conditional
+ * variant: context frames a [B][Ta][C][H][W] followed by generated frames b [B][Tb][C][H][W]).  Forward: dst =
+ * [B][C][Ta+Tb][H/2][W/2], the same per-element arithmetic as dvd_vid_downsample.  Backward: the arguments name the same tensors'
+ * gradients -- reads d(dst), writes d(b) into `b`; `a` is neither read nor written (may be null): context frames are data. */
+int dvd_vid_downsample_cat(const float* a, int Ta, float* b, int Tb, float* dst, int B, int C, int H, int W, int backward,
+                           void* stream);
 int dvd_row_copy(const float* src, float* dst, const int* idx, long long nrows, long long L, int scatter, void* stream);
 
 /* ------------------------------------------------------------------------------------------
