@@ -304,16 +304,99 @@ __global__ void adv_loss_kernel(const float* out, long long n, int hinge, int re
 
 // ----------------------------------------------------------------------------- Adam
 // torch.optim.Adam (no weight decay / amsgrad), trainer.py:136-141
+// One element of the update; adam_kernel and adam_ema_kernel share it so both produce the same bits.  Contraction is off:
+// whether a multiply and an add fuse must not depend on the kernel this is inlined into (adam_kernel compiles to separate
+// multiplies and adds, and its results are pinned by tests/test_gpu_ema.py against the fused launch).
+__device__ __forceinline__ float adam_elem(float pi, float gi, float& m, float& v, float lr_over_bc1, float b1, float b2,
+                                           float eps, float bc2_sqrt) {
+#pragma clang fp contract(off)
+    const float mi = m + (gi - m) * (1.f - b1);
+    const float vi = v * b2 + (1.f - b2) * gi * gi;
+    m = mi;
+    v = vi;
+    return pi - lr_over_bc1 * mi / (sqrtf(vi) / bc2_sqrt + eps);
+}
 __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long long n, float lr_over_bc1, float b1,
                             float b2, float eps, float bc2_sqrt) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float gi = g[i];
-    const float mi = m[i] + (gi - m[i]) * (1.f - b1);
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    float mi = m[i], vi = v[i];
+    const float pi = adam_elem(p[i], g[i], mi, vi, lr_over_bc1, b1, b2, eps, bc2_sqrt);
     m[i] = mi;
     v[i] = vi;
-    p[i] -= lr_over_bc1 * mi / (sqrtf(vi) / bc2_sqrt + eps);
+    p[i] = pi;
+}
+
+// ----------------------------------------------------------------------------- weight average (EMA)
+// ema = d * ema + (1 - d) * p as fmaf(d, ema, omd * p): d = 0 leaves ema == p bit for bit (omd = 1).
+__device__ __forceinline__ float ema_elem(float e, float p, float d, float omd) { return fmaf(d, e, omd * p); }
+
+// The three kernels below are memory-bound streams over flat fp32 buffers: a capped grid (FLAT_MAX_BLOCKS) walks n4 16-byte
+// vectors with a grid-stride loop, then the elements from 4 * n4 on one by one.  The host passes n4 = n / 4 when every pointer is
+// 16-byte aligned and n4 = 0 otherwise (the scalar loop then covers everything).
+constexpr unsigned FLAT_MAX_BLOCKS = 2048;          // 8 workgroups of 256 threads for each of the MI355X's 256 CUs
+
+// Adam (exactly adam_kernel's arithmetic) and the average of the UPDATED weights in one pass
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* p, const float* g, float* m, float* v, float* ema, long long n,
+                                                       long long n4, float lr_over_bc1, float b1, float b2, float eps,
+                                                       float bc2_sqrt, float d, float omd) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long long i = t; i < n4; i += stride) {
+        f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 mv = reinterpret_cast<const f32x4*>(m)[i], vv = reinterpret_cast<const f32x4*>(v)[i];
+        f32x4 ev = reinterpret_cast<const f32x4*>(ema)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float mk = mv[k], vk = vv[k];
+            const float pk = adam_elem(pv[k], gv[k], mk, vk, lr_over_bc1, b1, b2, eps, bc2_sqrt);
+            mv[k] = mk;
+            vv[k] = vk;
+            pv[k] = pk;
+            ev[k] = ema_elem(ev[k], pk, d, omd);
+        }
+        reinterpret_cast<f32x4*>(m)[i] = mv;
+        reinterpret_cast<f32x4*>(v)[i] = vv;
+        reinterpret_cast<f32x4*>(p)[i] = pv;
+        reinterpret_cast<f32x4*>(ema)[i] = ev;
+    }
+    for (long long i = n4 * 4 + t; i < n; i += stride) {
+        float mi = m[i], vi = v[i];
+        const float pi = adam_elem(p[i], g[i], mi, vi, lr_over_bc1, b1, b2, eps, bc2_sqrt);
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi;
+        ema[i] = ema_elem(ema[i], pi, d, omd);
+    }
+}
+
+__global__ __launch_bounds__(256) void ema_kernel(float* ema, const float* p, long long n, long long n4, float d, float omd) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long long i = t; i < n4; i += stride) {
+        const f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+        f32x4 ev = reinterpret_cast<const f32x4*>(ema)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ev[k] = ema_elem(ev[k], pv[k], d, omd);
+        reinterpret_cast<f32x4*>(ema)[i] = ev;
+    }
+    for (long long i = n4 * 4 + t; i < n; i += stride) ema[i] = ema_elem(ema[i], p[i], d, omd);
+}
+
+__global__ __launch_bounds__(256) void swap_kernel(float* a, float* b, long long n, long long n4) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long long i = t; i < n4; i += stride) {
+        const f32x4 av = reinterpret_cast<const f32x4*>(a)[i], bv = reinterpret_cast<const f32x4*>(b)[i];
+        reinterpret_cast<f32x4*>(a)[i] = bv;
+        reinterpret_cast<f32x4*>(b)[i] = av;
+    }
+    for (long long i = n4 * 4 + t; i < n; i += stride) {
+        const float ai = a[i], bi = b[i];
+        a[i] = bi;
+        b[i] = ai;
+    }
 }
 
 }  // namespace
@@ -442,5 +525,37 @@ extern "C" int dvd_adam_step(float* p, const float* g, float* m, float* v, long 
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     adam_kernel<<<cdiv(n, 256), 256, 0, S_>>>(p, g, m, v, n, (float)((double)lr / bc1), beta1, beta2, eps, (float)sqrt(bc2));
+    return launch_status();
+}
+
+// n4 of the flat kernels: whole 16-byte vectors when every pointer is 16-byte aligned, else 0 (all scalar)
+static inline long long flat_n4(long long n, uintptr_t ptr_bits) { return (ptr_bits & 15) ? 0 : n / 4; }
+static inline unsigned flat_grid(long long n, long long n4) {
+    const long long g = ((n4 ? n4 : n) + 255) / 256;          // capped before the narrowing: no wrap for any n
+    return g < (long long)FLAT_MAX_BLOCKS ? (unsigned)g : FLAT_MAX_BLOCKS;
+}
+static inline bool decay_ok(float d) { return d >= 0.f && d < 1.f; }      // false for NaN as well
+
+extern "C" int dvd_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr,
+                                 float beta1, float beta2, float eps, int step, float decay, void* stream) {
+    if (!p || !g || !m || !v || !ema || n <= 0 || step <= 0 || !decay_ok(decay)) return DVD_E_ARG;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    const long long n4 = flat_n4(n, (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema);
+    adam_ema_kernel<<<flat_grid(n, n4), 256, 0, S_>>>(p, g, m, v, ema, n, n4, (float)((double)lr / bc1), beta1, beta2, eps,
+                                                      (float)sqrt(bc2), decay, (float)(1.0 - (double)decay));
+    return launch_status();
+}
+extern "C" int dvd_ema_step(float* ema, const float* p, long long n, float decay, void* stream) {
+    if (!ema || !p || n <= 0 || !decay_ok(decay)) return DVD_E_ARG;
+    const long long n4 = flat_n4(n, (uintptr_t)ema | (uintptr_t)p);
+    ema_kernel<<<flat_grid(n, n4), 256, 0, S_>>>(ema, p, n, n4, decay, (float)(1.0 - (double)decay));
+    return launch_status();
+}
+extern "C" int dvd_swap_f32(float* a, float* b, long long n, void* stream) {
+    if (!a || !b || n <= 0) return DVD_E_ARG;
+    if (a == b) return DVD_OK;
+    const long long n4 = flat_n4(n, (uintptr_t)a | (uintptr_t)b);
+    swap_kernel<<<flat_grid(n, n4), 256, 0, S_>>>(a, b, n, n4);
     return launch_status();
 }

@@ -1,4 +1,6 @@
 """utils.py:60-63 / :77-83 of the reference on HIP kernels (reference-layout fp32 tensors)."""
+import math
+
 import torch
 
 from . import functional as Fn
@@ -45,3 +47,20 @@ def vid_downsample_cat(context, data):
 def denorm(x):
     """utils.py:41-43: [-1, 1] -> [0, 1], clamped."""
     return ((x + 1) / 2).clamp_(0, 1)
+
+
+def truncated_z(B, z_dim, tau, generator=None):
+    """[B, z_dim] fp32 draws of N(0, 1) truncated to [-tau, tau] (the truncation trick) by the inverse CDF:
+    sqrt(2) erfinv(2 p - 1) with p uniform in [Phi(-tau), Phi(tau)], in fp64, clamped, then rounded to float.  One uniform
+    draw per element from `generator` (default generator when None): no rejection loop, reproducible."""
+    tau = float(tau)
+    if not tau > 0.0:
+        raise ValueError(f"truncation={tau} must be positive")
+    lo = 0.5 * (1.0 + math.erf(-tau / math.sqrt(2.0)))
+    hi = 0.5 * (1.0 + math.erf(tau / math.sqrt(2.0)))
+    p = lo + (hi - lo) * torch.rand(B, z_dim, dtype=torch.float64, generator=generator)
+    z = math.sqrt(2.0) * torch.erfinv(2.0 * p - 1.0)
+    t32 = torch.tensor(tau, dtype=torch.float32)
+    if float(t32) > tau:                            # the largest float not above tau: |z| <= tau holds in exact arithmetic
+        t32 = torch.nextafter(t32, torch.zeros(()))
+    return z.clamp_(-tau, tau).float().clamp_(-float(t32), float(t32))

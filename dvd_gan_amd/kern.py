@@ -541,3 +541,19 @@ def embedding_backward(dout, idx, nrows, dW=None):
 def adam_step(p, g, m, v, lr, b1, b2, eps, step):
     L.check(L.lib().dvd_adam_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), _ll(p.numel()), _f(lr), _f(b1), _f(b2),
                                   _f(eps), int(step), L.stream()))
+
+
+def adam_ema_step(p, g, m, v, ema, lr, b1, b2, eps, step, decay):
+    """adam_step and ema = decay * ema + (1 - decay) * p_new in one launch."""
+    L.check(L.lib().dvd_adam_ema_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), _ll(p.numel()), _f(lr), _f(b1),
+                                      _f(b2), _f(eps), int(step), _f(decay), L.stream()))
+
+
+def ema_step(ema, p, decay):
+    L.check(L.lib().dvd_ema_step(L.ptr(ema), L.ptr(p), _ll(p.numel()), _f(decay), L.stream()))
+
+
+def swap_(a, b):
+    """Exchange the contents of two fp32 tensors of equal size."""
+    assert a.numel() == b.numel() and a.dtype == b.dtype == torch.float32
+    L.check(L.lib().dvd_swap_f32(L.ptr(a), L.ptr(b), _ll(a.numel()), L.stream()))

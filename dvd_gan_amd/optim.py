@@ -4,6 +4,9 @@ torch.optim.Adam(lr, betas=(beta1, beta2)) on the requires_grad parameters).
 The trainable parameters of a network are re-homed as views into ONE contiguous buffer, their
 .grad tensors are views into a second one.  That makes the optimizer a single elementwise launch
 and the data-parallel gradient exchange a single RCCL all-reduce per network.
+
+ema_decay > 0 adds an exponential moving average of the weights (`ema`, the BigGAN-family sampling weights), updated in
+the same launch from the weights that launch has just written.
 """
 import torch
 
@@ -11,7 +14,13 @@ from . import kern as K
 
 
 class FlatAdam:
-    def __init__(self, params, lr, betas=(0.0, 0.9), eps=1e-8):
+    def __init__(self, params, lr, betas=(0.0, 0.9), eps=1e-8, ema_decay=0.0, ema_start=0):
+        """ema_decay = 0: no average (`ema` stays None, step() is dvd_adam_step).  Otherwise `ema` is allocated as a copy of
+        `flat` at the first step() -- the weights training starts from, whatever was loaded or broadcast into `flat` after
+        construction -- or set by load_ema(); it follows the weights (decay 0) while t <= ema_start, then decays by ema_decay."""
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"ema_decay={ema_decay} must lie in [0, 1)")
+        self.ema_decay, self.ema_start, self.ema = float(ema_decay), int(ema_start), None
         self.params = [p for p in params if p.requires_grad]
         dev = self.params[0].device
         n = sum(p.numel() for p in self.params)
@@ -45,7 +54,23 @@ class FlatAdam:
                 p.grad = view
             off += k
 
+    def load_ema(self, flat_tensor):
+        """Set the average (a flat fp32 tensor laid out like `flat`)."""
+        if not self.ema_decay:
+            raise RuntimeError("this optimizer keeps no weight average (ema_decay = 0)")
+        if flat_tensor.numel() != self.flat.numel():
+            raise ValueError(f"average of {flat_tensor.numel()} elements for {self.flat.numel()} parameters")
+        if self.ema is None:
+            self.ema = torch.empty_like(self.flat)
+        self.ema.copy_(flat_tensor.reshape(-1))
+
     def step(self):
         self.t += 1
+        if self.ema_decay:
+            if self.ema is None:
+                self.ema = self.flat.clone()
+            K.adam_ema_step(self.flat, self.grad, self.m, self.v, self.ema, self.param_groups[0]["lr"], self.betas[0],
+                            self.betas[1], self.eps, self.t, 0.0 if self.t <= self.ema_start else self.ema_decay)
+            return
         K.adam_step(self.flat, self.grad, self.m, self.v, self.param_groups[0]["lr"], self.betas[0], self.betas[1],
                     self.eps, self.t)

@@ -215,6 +215,7 @@ class ConditionalNorm(nn.Module):
         self.embed.bias = nn.Parameter(b)
         self.replicas = None               # (world, all_reduce_sum_) when batch statistics span all replicas
         self._sums = None                  # persistent fp64 workspace of the statistics kernel (left zeroed by dvd_bn_finalize)
+        self.momentum = 0.1                # of the running statistics (Trainer.ema_weights sets 1 / i for standing statistics)
         self.count_batches = True          # False: a caller (the Generator) advances num_batches_tracked for all layers at once
 
     def forward(self, x, cond, samp, relu=True, tok=None, slot=None):
@@ -225,4 +226,4 @@ class ConditionalNorm(nn.Module):
         if self._sums is None or self._sums.device != x.device:
             self._sums = torch.zeros(L.BN_NREP * 2 * self.in_channel, dtype=torch.float64, device=x.device)
         return Fn.CondBatchNorm.apply(x, gb, samp, self.in_channel, relu, self.training, self.bn.running_mean,
-                                      self.bn.running_var, 1e-5, 0.1, self.replicas, self._sums, tok, slot)
+                                      self.bn.running_var, 1e-5, self.momentum, self.replicas, self._sums, tok, slot)

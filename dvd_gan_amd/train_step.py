@@ -11,20 +11,26 @@ n_frames targets; the generator encodes the context (cond_encoder.FrameEncoder),
 ones, D_t judges whole clips -- the real clip against [context | generated].
 Differences that do not change results: the dead D weight-gradients of the generator step are not
 computed; Adam is one fused launch per network; gradients are exchanged with RCCL (dist.py).
+Beyond the reference: config.ema_decay > 0 keeps an exponential moving average of the generator's weights, updated inside the
+generator's Adam launch (optim.FlatAdam); `ema_weights()` / `sample(use_ema=True)` / `predict(use_ema=True)` compute with it and
+`save_models` writes it as `{step}_G_ema.pth`.
 Out of scope: tensorboard logging, sample grids, dataset loaders.
 """
+import contextlib
 import os
 import time
 
 import torch
 
 from . import functional as Fn
+from . import kern as K
 from . import lib as L
 from . import dist as D
 from .dist import GradExchange
 from .disc_nets import SpatialDiscriminator, TemporalDiscriminator
 from .gen_net import Generator
-from .helpers import denorm, draw_frame_ids, sample_k_frames, to_device_async, vid_downsample, vid_downsample_cat
+from .helpers import (denorm, draw_frame_ids, sample_k_frames, to_device_async, truncated_z, vid_downsample,
+                      vid_downsample_cat)
 from .optim import FlatAdam
 
 
@@ -113,6 +119,15 @@ class Trainer(object):
             # D_t sees context + generated frames and pools time twice (TemporalDiscriminator._forward)
             raise ValueError(f"n_cond + n_frames = {self.n_cond + self.n_frames} must be a multiple of 4: D_t judges the context "
                              "and the generated frames together and pools time twice")
+        # generator weight average (0 = off): decay, steps it merely follows the weights, standing-statistics passes at
+        # sampling / saving time and the seed of their private noise generator
+        self.ema_decay = float(getattr(c, "ema_decay", 0.0))
+        self.ema_start = int(getattr(c, "ema_start", 0))
+        self.ema_standing_stats = int(getattr(c, "ema_standing_stats", 0))
+        self.ema_stats_seed = int(getattr(c, "ema_stats_seed", 0))
+        if not 0.0 <= self.ema_decay < 1.0 or self.ema_start < 0 or self.ema_standing_stats < 0:
+            raise ValueError(f"ema_decay={self.ema_decay} (in [0, 1)), ema_start={self.ema_start}, "
+                             f"ema_standing_stats={self.ema_standing_stats} (both >= 0)")
         self.lr_decay = getattr(c, "lr_decay", 0.9999)
         self.pretrained_model = getattr(c, "pretrained_model", None)
         self.model_save_path = os.path.join(getattr(c, "model_save_path", "./models"), getattr(c, "version", ""))
@@ -180,7 +195,7 @@ class Trainer(object):
     # ---- trainer.py:134-176
     def select_opt_schr(self):
         betas = (self.beta1, self.beta2)
-        self.g_optimizer = FlatAdam(self.G.parameters(), self.g_lr, betas)
+        self.g_optimizer = FlatAdam(self.G.parameters(), self.g_lr, betas, ema_decay=self.ema_decay, ema_start=self.ema_start)
         # (the optional attention blocks and the conditioning encoder sit at the END of the parameter order but finish their
         #  gradients late in the backward pass -- the encoder's last of all, behind the dh0 of the first ConvGRU: with them the
         #  generator's gradient goes in one piece)
@@ -405,45 +420,161 @@ class Trainer(object):
             if self.model_save_epoch and step % (self.model_save_epoch * steps_per_epoch) == 0:
                 self.save_models(step)
 
+    # ---- the averaged generator weights
+    def _ema_on(self):
+        return bool(getattr(getattr(self, "g_optimizer", None), "ema_decay", 0.0))
+
+    def _g_frozen_tensors(self):
+        """Every tensor of G that Adam does not own: spectral-norm u / v, batch-norm running statistics and counters."""
+        return [p.data for p in self.G.parameters() if not p.requires_grad] + list(self.G.buffers())
+
+    def standing_draws(self, generator, batch):
+        """z [batch, z_dim] and labels [batch] of ONE standing-statistics pass, in the order the passes draw them."""
+        z = torch.randn(batch, self.z_dim, generator=generator)
+        return z, torch.randint(0, self.n_class, (batch,), generator=generator)
+
+    @contextlib.contextmanager
+    def ema_weights(self, standing_stats=0, cond=None, labels=None):
+        """Inside the block `self.G` computes with the averaged weights: the average and the live weights are exchanged in
+        place (dvd_swap_f32) on entry and exchanged back on exit, and every tensor of G that is not a trained weight (spectral-
+        norm u / v, batch-norm running statistics and counters) is put back as it was -- training state after the block is
+        bit-equal to before it.  Before the first optimizer step the average IS the weights and nothing is exchanged.
+        Not re-entrant: a second block inside the first would exchange the live weights back in, so it raises.
+        standing_stats = N > 0: on entry, after the exchange, the running statistics are re-estimated for the averaged weights
+        by N train-mode forward passes without gradients, pass i with batch-norm momentum 1 / i (a cumulative average from
+        scratch), on z / labels from a private generator seeded with config.ema_stats_seed (the default generator is not
+        touched).  A frame-conditional generator runs them on the caller's `cond` / `labels`."""
+        if not self._ema_on():
+            raise RuntimeError("no weight average is configured (config.ema_decay = 0)")
+        if getattr(self, "_ema_block", False):
+            raise RuntimeError("ema_weights() is already active: the block does not nest (save_models and sample / predict with "
+                               "use_ema=True enter it themselves)")
+        from .sn_layers import ConditionalNorm
+        opt, G = self.g_optimizer, self.G
+        n_pass = int(standing_stats or 0)
+        if n_pass and self.n_cond and (cond is None or labels is None):
+            raise ValueError("standing statistics of a frame-conditional generator need the caller's `cond` and `labels`")
+        frozen = self._g_frozen_tensors()
+        saved = [t.clone() for t in frozen]
+        norms = [m for m in G.modules() if isinstance(m, ConditionalNorm)]
+        momenta, was_training = [m.momentum for m in norms], G.training
+        swapped = opt.ema is not None
+        self._ema_block = True
+        if swapped:
+            K.swap_(opt.flat, opt.ema)
+        try:
+            if n_pass:
+                gen = torch.Generator().manual_seed(self.ema_stats_seed)
+                B = cond.shape[0] if self.n_cond else self.batch_size
+                G.train()
+                for m in norms:                    # from scratch: nothing of the live statistics (a NaN included) survives
+                    m.bn.num_batches_tracked.zero_()
+                    m.bn.running_mean.zero_()
+                    m.bn.running_var.fill_(1.0)
+                with torch.no_grad():
+                    for i in range(1, n_pass + 1):
+                        for m in norms:
+                            m.momentum = 1.0 / i
+                        z, y = self.standing_draws(gen, B)
+                        if self.n_cond:
+                            G(z.to(self.device), self._check_labels(labels).to(self.device), cond=cond.to(self.device, torch.float32))
+                        else:
+                            G(z.to(self.device), y.to(self.device))
+                for m, mom in zip(norms, momenta):
+                    m.momentum = mom
+                G.train(was_training)
+            yield self.G
+        finally:
+            for m, mom in zip(norms, momenta):
+                m.momentum = mom
+            G.train(was_training)
+            if swapped:
+                K.swap_(opt.flat, opt.ema)
+            for t, old in zip(frozen, saved):
+                t.copy_(old)
+            self._ema_block = False
+
+    def _sampling_weights(self, use_ema, standing_stats, cond=None, labels=None):
+        if not use_ema:
+            if standing_stats:
+                raise ValueError("standing_stats re-estimates the statistics of the averaged weights: it needs use_ema=True")
+            return contextlib.nullcontext()
+        if not self._ema_on():
+            raise RuntimeError("use_ema=True, but no weight average is configured (config.ema_decay = 0)")
+        n = self.ema_standing_stats if standing_stats is None else int(standing_stats)
+        return self.ema_weights(n, cond=cond, labels=labels)
+
+    def _draw_z(self, batch, truncation):
+        if truncation is None:
+            return torch.randn(batch, self.z_dim, generator=self.noise_gen)
+        return truncated_z(batch, self.z_dim, truncation, generator=self.noise_gen)
+
     # ---- trainer.py:323-334: the sampling path (eval-mode G on fixed z / labels, BN running statistics), without
     # the image-file side (torchvision save_image / tensorboard are host plumbing, DESIGN section 8)
     @torch.no_grad()
-    def sample(self, fixed_z, fixed_label):
+    def sample(self, fixed_z, fixed_label, *, use_ema=False, standing_stats=None, truncation=None):
         """-> denorm(G(fixed_z, fixed_label)) [B, T, 3, H, W] in [0, 1]; G is put back in train mode, like the reference.
-        Note quirk 2: the spectral-norm u/v of G advance in eval mode as well."""
+        Note quirk 2: the spectral-norm u/v of G advance in eval mode as well.
+        use_ema: compute with the averaged weights (ema_weights(); the training state is left untouched, u / v included);
+        standing_stats: passes that re-estimate the batch-norm statistics for them (None = config.ema_standing_stats).
+        fixed_z = None draws z here, truncation = tau from N(0, 1) truncated to [-tau, tau] (helpers.truncated_z)."""
         if self.n_cond:
             raise RuntimeError("a frame-conditional generator (n_cond > 0) continues clips: use Trainer.predict(cond, labels)")
-        self.G.eval()
-        fake = self.G(fixed_z.to(self.device), fixed_label.to(self.device))
-        self.G.train()
+        if fixed_z is None:
+            fixed_z = self._draw_z(fixed_label.shape[0], truncation)
+        elif truncation is not None:
+            raise ValueError("truncation applies to z drawn here: pass fixed_z=None, or truncate the z you pass")
+        with self._sampling_weights(use_ema, standing_stats):
+            self.G.eval()
+            try:
+                fake = self.G(fixed_z.to(self.device), fixed_label.to(self.device))
+            finally:
+                self.G.train()
         return denorm(fake)
 
     @torch.no_grad()
-    def predict(self, cond, labels, z=None):
+    def predict(self, cond, labels, z=None, *, use_ema=False, standing_stats=None, truncation=None):
         """Frame-conditional prediction (n_cond = K > 0): cond [B, K, 3, H, W] context frames in [-1, 1] (the generator's output
         layout, so denormalised predictions come back in as 2 p - 1), labels [B] -> denorm(G(z, labels, cond=cond)), the next
-        n_frames frames [B, T, 3, H, W] in [0, 1].  z [B, z_dim] defaults to a fresh draw.  Eval / train mode as in sample()."""
+        n_frames frames [B, T, 3, H, W] in [0, 1].  z [B, z_dim] defaults to a fresh draw (truncated to [-truncation,
+        truncation] when that is given).  Eval / train mode, use_ema and standing_stats as in sample(); the standing-statistics
+        passes run on this call's cond / labels."""
         if not self.n_cond:
             raise RuntimeError("predict() needs a frame-conditional Trainer (config.n_cond > 0); use sample()")
         B = cond.shape[0]
         if z is None:
-            z = torch.randn(B, self.z_dim, generator=self.noise_gen)
-        self.G.eval()
-        try:
-            fake = self.G(z.to(self.device), self._check_labels(labels).to(self.device), cond=cond.to(self.device, torch.float32))
-        finally:
-            self.G.train()
+            z = self._draw_z(B, truncation)
+        elif truncation is not None:
+            raise ValueError("truncation applies to z drawn here: pass z=None, or truncate the z you pass")
+        with self._sampling_weights(use_ema, standing_stats, cond, labels):
+            self.G.eval()
+            try:
+                fake = self.G(z.to(self.device), self._check_labels(labels).to(self.device), cond=cond.to(self.device, torch.float32))
+            finally:
+                self.G.train()
         return denorm(fake)
 
     # ---- trainer.py:337-343 / 375-382: reference-compatible checkpoints
     def save_models(self, step):
-        """Rank 0 writes (its batch-norm running statistics are the ones saved in "replica" mode); the others wait."""
+        """Rank 0 writes (its batch-norm running statistics are the ones saved in "replica" mode); the others wait.
+        With a weight average (config.ema_decay > 0) a fourth file `{step}_G_ema.pth` holds G.state_dict() taken inside
+        ema_weights(standing_stats=config.ema_standing_stats): the keys of `{step}_G.pth`, loadable into a plain Generator.  A
+        frame-conditional Trainer has no context frames at this point: its file carries the averaged weights with the LIVE
+        running statistics whatever ema_standing_stats says.  In a data-parallel run every rank enters the block and runs
+        the standing-statistics passes (same seed: cross-replica collectives pair up); rank 0 writes."""
         world = D.world_size()
-        if world == 1 or torch.distributed.get_rank() == 0:
+        writer = world == 1 or torch.distributed.get_rank() == 0
+        if writer:
             os.makedirs(self.model_save_path, exist_ok=True)
             for net, tag in ((self.G, "G"), (self.D_s, "Ds"), (self.D_t, "Dt")):
                 torch.save({k: v.detach().cpu() for k, v in net.state_dict().items()},
                            os.path.join(self.model_save_path, "{}_{}.pth".format(step, tag)))
+        if self._ema_on():
+            n_pass = 0 if getattr(self, "n_cond", 0) else getattr(self, "ema_standing_stats", 0)
+            with self.ema_weights(standing_stats=n_pass):
+                if writer:
+                    torch.save({k: v.detach().cpu() for k, v in self.G.state_dict().items()},
+                               os.path.join(self.model_save_path, "{}_G_ema.pth".format(step)))
         if world > 1:
             torch.distributed.barrier()
 
@@ -453,3 +584,11 @@ class Trainer(object):
                             map_location="cpu")
             sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}     # DataParallel prefix
             net.load_state_dict(sd)
+        # the average: its own file when there is one, else it starts from the weights just loaded (FlatAdam copies them at
+        # the first step)
+        path = os.path.join(self.model_save_path, "{}_G_ema.pth".format(self.pretrained_model))
+        if self._ema_on() and os.path.exists(path):
+            sd = torch.load(path, map_location="cpu")
+            sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+            flat = torch.cat([sd[k].reshape(-1).float() for k, p in self.G.named_parameters() if p.requires_grad])
+            self.g_optimizer.load_ema(flat.to(self.g_optimizer.flat.device))

@@ -403,6 +403,18 @@ int dvd_adv_loss(const float* out, long long n, int hinge, int real_flag, float*
 /* torch.optim.Adam.step (trainer.py:252,268,306) on one flat fp32 buffer */
 int dvd_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                   float eps, int step, void* stream);
+/* Generator weight average (optim.FlatAdam(ema_decay > 0).step): dvd_adam_step's arithmetic, then
+ * ema = decay * ema + (1 - decay) * p_new in the same launch; (1 - decay) is formed in double and rounded once, decay = 0 gives
+ * ema == p_new bit for bit.  decay in [0, 1).  Any pointer alignment (16-byte aligned buffers take the vector path).
+ * The five buffers must not overlap one another (not checked). */
+int dvd_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr, float beta1,
+                      float beta2, float eps, int step, float decay, void* stream);
+/* The averaging line alone (callers that step their weights differently; tests/test_gpu_ema.py proves the fused form with it).
+ * ema and p must not overlap (not checked). */
+int dvd_ema_step(float* ema, const float* p, long long n, float decay, void* stream);
+/* Exchange two fp32 buffers in place (Trainer.ema_weights: live weights <-> average around a sampling block).  a == b is a
+ * no-op; buffers that overlap in part are not supported (not checked: both would be corrupted). */
+int dvd_swap_f32(float* a, float* b, long long n, void* stream);
 
 /* 2-D self attention (Discriminators.py:100-119: bmm, softmax, bmm, gamma*out + x) */
 int dvd_attention_forward(int dtype, const void* qkv, int ldq, int dq, int koff, int voff, const void* x, int ldx, int C,
