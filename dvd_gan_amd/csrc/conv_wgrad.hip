@@ -1,6 +1,11 @@
-// Weight gradients of the convolutions: conv_wgrad_row_kernel (one filter row per workgroup, 3 x 3 / 5 x 5 / 3 x 3 x 3) and
-// conv_wgrad_kernel (one tap per workgroup: 1 x 1, upsampling and exact-mode convolutions), their fixed-order reduce kernels,
-// and the C ABI entry dvd_conv_wgrad.
+// Weight gradients of the convolutions and the C ABI entries dvd_conv_wgrad / dvd_conv_wgrad_ws_floats.  Three kernel families:
+//   conv_wgrad_kernel       one tap per workgroup: 1 x 1, exact-mode (f32) and every shape the filter-row kernels do not take
+//   conv_wgrad_row_kernel   one filter row per workgroup, 8 (4, 2) waves: 3 x 3 / 5 x 5 / 3 x 3 x 3, also over an x2-upsampled input
+//   conv_wgrad_row4_kernel  one filter row per workgroup, ONE WAVE PER SIMD with the whole register file: the large 3- and 5-tap
+//                           launches, and (FOLD) the 3 x 3 layers over an x2-upsampled input worked on the input grid
+// Row slices either add into dw with atomics (a single slice) or leave partial tiles in the slice workspace (ws_tile_off /
+// ws_bias_off: the one place its layout is written down) for the fixed-order reduce kernels.  The host side is a planner in named
+// steps (wg_fill_request, wg_choose_tile, wg_choose_split -> one WgPlan) and a table-driven dispatch (wg_launch).
 #include "conv_common.h"
 #include "prof.h"
 #include <cstdlib>
@@ -19,11 +24,88 @@ struct WgK {
     size_t x_bytes, dy_bytes;
     int maxshift, xcd_remap;
     float* dbias;
-    float* wsb;             // row kernel, workspace path: bias partial sums [slice][workgroup][BMc] behind the tile partials
-    float* ws;                           // partial tiles [slice][x-block][BMc*BNc] when non-null
+    float* wsb;                          // workspace path: the bias partials behind the tile partials (ws_bias_off)
+    float* ws;                           // slice workspace when non-null: partial tiles (ws_tile_off)
     int fold, cout_f;                    // conv_wgrad_row4_kernel<FOLD>: x2-upsampled input folded onto the input grid (cout_f = the layer's Cout)
 };
 
+// ---------------------------------------------------------------------------- slice workspace layout
+// Partial tiles [slice][workgroup][tap of the row][BMc][BNc] (kw = 1 for the one-tap kernel), then the bias partials
+// [slice][workgroup][BMc] (filter-row kernels) or [slice][tco][BMc] (one-tap kernel).  Kernel epilogues, reduce kernels and the host's
+// workspace size (WgPlan) all go through these two functions.
+// (G / N: the count's own integer type -- gridDim.x is unsigned, the reduce kernels' and the host's counts are signed)
+template <typename G>
+__host__ __device__ __forceinline__ size_t ws_tile_off(size_t slice, G gx, int bx, int kw, int t, int tile_elems) { return ((slice * gx + bx) * kw + t) * (size_t)tile_elems; }
+template <typename G>     // floats from a partial tile to the same tile of the next slice
+__host__ __device__ __forceinline__ size_t ws_slice_stride(G gx, int kw, int tile_elems) { return ws_tile_off(1, gx, 0, kw, 0, tile_elems); }
+template <typename N>
+__host__ __device__ __forceinline__ size_t ws_bias_off(size_t slice, N n, int i, int BMc) { return (slice * n + i) * BMc; }
+
+// ---------------------------------------------------------------------------- shared prologue / epilogue of the three kernels
+// XCD-aware order over (x, z): each XCD gets a contiguous run of row slices, whose workgroups (all
+// taps / channel tiles of a slice) then share the slice's rows in that XCD's L2 (hit rate 0.42 -> 0.73
+// on the 3x3 shapes, 0.81 -> 0.89 on the 5x5 ones; tools/pmc_l2.txt)
+__device__ __forceinline__ void xcd_block_remap(const WgK& p, int& bx, int& bz) {
+    bx = blockIdx.x; bz = blockIdx.z;
+    if (p.xcd_remap) {
+        const int gx = gridDim.x, total = gx * gridDim.z, lin = bx + gx * bz;
+        const int xcd = lin & 7, qd = total >> 3, rr = total & 7;
+        const int lp = (xcd < rr ? xcd * (qd + 1) : rr * (qd + 1) + (xcd - rr) * qd) + (lin >> 3);
+        bz = lp / gx; bx = lp - bz * gx;
+    }
+}
+// the eight bf16 of a staged 16-byte dy chunk as floats (bias column sums)
+__device__ __forceinline__ void bf16x8_unpack(const u32x4& r, float (&v)[8]) {
+    v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u);
+    v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
+    v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u);
+    v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
+}
+// Finish of the bias column sums, NV per thread (the channels of its dy chunk): TAB is thread (r * CPRA + tid)'s sum k, an expression in
+// r and k; the RPPA threads that share a channel chunk are added in order of r.  The result is bias partial (bz, I) of N per slice in
+// the workspace (TO_WS), or one atomic addition per channel.  (The two tails are macros, not functions: as inlined functions they
+// changed the generated code of all 38 conv kernels, main loops included, and the time of two of them by 2-3 %.  Both expand in a
+// kernel body and use its p, tid / lane, co0, ci0, bz, bx, BMc, BNc; WG_TILE_TAIL also ep, the wave's 32 x 32 float LDS block.)
+#define WG_BIAS_FINISH(CPRA, RPPA, NV, TAB, TO_WS, N, I)                                                                \
+    do {                                                                                                                \
+        __syncthreads();                                                                                                \
+        if (tid < CPRA) {                                                                                               \
+            for (int k = 0; k < NV; ++k) {                                                                              \
+                float a = 0.f;                                                                                          \
+                for (int r = 0; r < RPPA; ++r) a += TAB;                                                                \
+                const int co = co0 + tid * NV + k;                                                                      \
+                if (TO_WS) p.wsb[ws_bias_off(bz, N, I, BMc) + tid * NV + k] = a;                                        \
+                else if (co < p.Cout && a != 0.f) atomicAdd(p.dbias + co, a);     /* a single slice: one addition per channel */ \
+            }                                                                                                           \
+        }                                                                                                               \
+        __syncthreads();                                                                                                \
+    } while (0)
+// Tail of one 32 x 32 accumulator tile ACC, whose corner is (ROW0, COL0) of the workgroup tile: through the wave's LDS block `ep`, then
+// either plain coalesced stores into partial tile (bz, bx, T) of the slice workspace (tile-local [row][col] layout) or a rolled loop
+// of atomics into dw (an unrolled 128-atomic epilogue costs ~170 VGPRs of addresses).
+#define WG_TILE_TAIL(ACC, ROW0, COL0, KW_, T, TAP)                                                                      \
+    do {                                                                                                                \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r)                                                                  \
+            ep[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = ACC[r];                                 \
+        __builtin_amdgcn_s_waitcnt(0xc07f);                                                                             \
+        __builtin_amdgcn_wave_barrier();                                                                                \
+        const int ci = ci0 + COL0 + (lane & 31);                                                                        \
+        const int cob = co0 + ROW0 + (lane >> 5);                                                                       \
+        const int wtap = TAP;                 /* ahead of the branch, where the kernels had it: inside, their code changes */  \
+        if (p.ws) {                                                                                                     \
+            float* wt = p.ws + ws_tile_off(bz, gridDim.x, bx, KW_, T, BMc * BNc) + (size_t)(ROW0) * BNc + COL0;         \
+            _Pragma("unroll 1") for (int j = 0; j < 16; ++j)                                                            \
+                wt[(size_t)(2 * j + (lane >> 5)) * BNc + (lane & 31)] = ep[(2 * j + (lane >> 5)) * 32 + (lane & 31)];   \
+        } else if (ci < p.Cin_real) {                                                                                   \
+            float* dst = p.dw + ci * p.s_ci + wtap * p.s_tap;                                                           \
+            _Pragma("unroll 1") for (int j = 0; j < 16; ++j) {                                                          \
+                const int co = cob + 2 * j;                                                                             \
+                const float v = ep[(2 * j + (lane >> 5)) * 32 + (lane & 31)];                                           \
+                if (co < p.Cout && v != 0.f) atomicAdd(dst + co * p.s_co, v);                                           \
+            }                                                                                                           \
+        }                                                                                                               \
+        __builtin_amdgcn_wave_barrier();                                                                                \
+    } while (0)
 // D[co][ci] = sum over rows m of dy[m][co] * x[pos(m)+tap][ci].  The reduction index (rows) is the
 // MFMA K dimension, so both operand tiles must be K(row)-contiguous per channel in LDS:
 //   bf16: tiles are staged in their natural [row][channel] image with 16-byte loads and the
@@ -40,16 +122,8 @@ __global__ __launch_bounds__(NT) void conv_wgrad_kernel(WgK p) {
     __shared__ __attribute__((aligned(16))) char smem[2][TA_BYTES + TB_BYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware order over (x, z): each XCD gets a contiguous run of row slices, whose workgroups (all
-    // taps / channel tiles of a slice) then share the slice's rows in that XCD's L2 (hit rate 0.42 -> 0.73
-    // on the 3x3 shapes, 0.81 -> 0.89 on the 5x5 ones; tools/pmc_l2.txt)
-    int bx = blockIdx.x, bz = blockIdx.z;
-    if (p.xcd_remap) {
-        const int gx = gridDim.x, total = gx * gridDim.z, lin = bx + gx * bz;
-        const int xcd = lin & 7, qd = total >> 3, rr = total & 7;
-        const int lp = (xcd < rr ? xcd * (qd + 1) : rr * (qd + 1) + (xcd - rr) * qd) + (lin >> 3);
-        bz = lp / gx; bx = lp - bz * gx;
-    }
+    int bx, bz;
+    xcd_block_remap(p, bx, bz);
     const int tiles = p.tiles_co * p.tiles_ci;
     const int tap = bx / tiles;
     const int rem = bx - tap * tiles;
@@ -197,17 +271,8 @@ __global__ __launch_bounds__(NT) void conv_wgrad_kernel(WgK p) {
             float* red = reinterpret_cast<float*>(&smem[0][0]);
 #pragma unroll
             for (int k = 0; k < 8; ++k) red[tid * 8 + k] = bs[k];
-            __syncthreads();
-            if (tid < CPRA) {
-                for (int k = 0; k < 8; ++k) {
-                    float a = 0.f;
-                    for (int r = 0; r < RPPA; ++r) a += red[(r * CPRA + tid) * 8 + k];
-                    const int co = co0 + tid * 8 + k;
-                    if (p.wsb) p.wsb[((size_t)bz * p.tiles_co + tco) * BMc + tid * 8 + k] = a;     // partial of (slice, channel tile): wgrad_bias_reduce_kernel
-                    else if (co < p.Cout && a != 0.f) atomicAdd(p.dbias + co, a);                  // (a single slice: one addition per channel)
-                }
-            }
-            __syncthreads();
+            // workspace path: partial of (slice, channel tile) for wgrad_bias_reduce_kernel
+            WG_BIAS_FINISH(CPRA, RPPA, 8, red[(r * CPRA + tid) * 8 + k], p.wsb, p.tiles_co, tco);
         }
     } else {
         // f32: LDS image [16 rows][WG_LD floats]; thread stages rows kr, kr+8, 16-byte chunk ch
@@ -264,27 +329,17 @@ __global__ __launch_bounds__(NT) void conv_wgrad_kernel(WgK p) {
             float* red = reinterpret_cast<float*>(&smem[0][0]);
 #pragma unroll
             for (int k = 0; k < 4; ++k) red[tid * 4 + k] = bs[k];
-            __syncthreads();
-            if (tid < 32) {
-                for (int k = 0; k < 4; ++k) {
-                    float a = 0.f;
-                    for (int r = 0; r < 8; ++r) a += red[(r * 32 + tid) * 4 + k];
-                    const int co = co0 + tid * 4 + k;
-                    if (p.wsb) p.wsb[((size_t)bz * p.tiles_co + tco) * BMc + tid * 4 + k] = a;
-                    else if (co < p.Cout && a != 0.f) atomicAdd(p.dbias + co, a);
-                }
-            }
-            __syncthreads();
+            WG_BIAS_FINISH(32, 8, 4, red[(r * 32 + tid) * 4 + k], p.wsb, p.tiles_co, tco);
         }
     }
 
-    // epilogue: each 32x32 accumulator tile goes through a per-wave LDS block and is then added to
-    // dw with a rolled loop (an unrolled 128-atomic epilogue costs ~170 VGPRs of addresses)
+    // epilogue: each 32 x 32 accumulator tile goes through a per-wave LDS block, then to the slice workspace or into dw
     float* ep = reinterpret_cast<float*>(&smem[0][0]) + wave * (32 * 32);
 #pragma unroll
     for (int ta = 0; ta < TA; ++ta)
 #pragma unroll
         for (int tb = 0; tb < TB; ++tb) {
+            // (WG_TILE_TAIL written out: this kernel forms the dw address ahead of the branch, and moving it renumbers its main loop)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 ep[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = acc[ta][tb][r];
@@ -294,8 +349,7 @@ __global__ __launch_bounds__(NT) void conv_wgrad_kernel(WgK p) {
             const int cob = co0 + wm * (TA * 32) + ta * 32 + (lane >> 5);
             float* dst = p.dw + ci * p.s_ci + tap * p.s_tap;
             if (p.ws) {
-                // partial tile of this row slice, tile-local [row][col] layout, coalesced plain stores
-                float* wt = p.ws + ((size_t)bz * gridDim.x + bx) * (size_t)(BMc * BNc) +
+                float* wt = p.ws + ws_tile_off(bz, gridDim.x, bx, 1, 0, BMc * BNc) +
                             (size_t)(wm * (TA * 32) + ta * 32) * BNc + wn * (TB * 32) + tb * 32;
 #pragma unroll 1
                 for (int j = 0; j < 16; ++j)
@@ -311,7 +365,6 @@ __global__ __launch_bounds__(NT) void conv_wgrad_kernel(WgK p) {
             __builtin_amdgcn_wave_barrier();
         }
 }
-
 // ============================================================================ backward-weight, one filter ROW per workgroup
 // Same contraction as conv_wgrad_kernel, regrouped so the staged operands are reused across taps: a workgroup owns
 // (filter row iy, 64*WM out-channels, 64 in-channels) and ALL KW taps of that row.  Per 32-pixel step it stages
@@ -346,21 +399,14 @@ __global__ __launch_bounds__(WM * NH * 64) void conv_wgrad_row_kernel(WgK p) {
     constexpr int SUB = TA_BYTES + TB_BYTES, STAGE = NS * SUB;
     constexpr int EPIB = NWAVE * 32 * 32 * 4;
     constexpr int REDB = NTt * 8 * 4;                            // bias partial sums
-    // 8-wave tiles sit at the 256-register limit: their bias column sums live in an LDS table behind the stage buffers (ds_add_f32 on
-    // the thread's own slots, same order of additions as the register form) instead of eight registers held through the main loop
-    constexpr bool BLDS = false;      // (measured: ds_add_f32 on a [8][threads] table costs 40-170 % on launches WITH a bias gradient -- registers it is)
-    constexpr int LDSB0 = 2 * STAGE > EPIB ? (2 * STAGE > REDB ? 2 * STAGE : REDB) : (EPIB > REDB ? EPIB : REDB);
-    constexpr int LDSB = LDSB0 + (BLDS ? REDB : 0);
+    // (the bias column sums are eight registers held through the main loop, also on the 8-wave tiles at the 256-register limit: an LDS
+    // table updated with ds_add_f32 cost 40-170 % on launches WITH a bias gradient)
+    constexpr int LDSB = 2 * STAGE > EPIB ? (2 * STAGE > REDB ? 2 * STAGE : REDB) : (EPIB > REDB ? EPIB : REDB);
     __shared__ __attribute__((aligned(16))) char smem[LDSB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / NH, wn = wave % NH;
-    int bx = blockIdx.x, bz = blockIdx.z;
-    if (p.xcd_remap) {
-        const int gx = gridDim.x, total = gx * gridDim.z, lin = bx + gx * bz;
-        const int xcd = lin & 7, qd = total >> 3, rr = total & 7;
-        const int lp = (xcd < rr ? xcd * (qd + 1) : rr * (qd + 1) + (xcd - rr) * qd) + (lin >> 3);
-        bz = lp / gx; bx = lp - bz * gx;
-    }
+    int bx, bz;
+    xcd_block_remap(p, bx, bz);
     const int tiles = p.tiles_co * p.tiles_ci;
     const int irow = bx / tiles;                                 // filter row index: it * kh + iy
     const int rem = bx - irow * tiles;
@@ -535,11 +581,6 @@ __global__ __launch_bounds__(WM * NH * 64) void conv_wgrad_row_kernel(WgK p) {
     const int nshare = spread ? KW * p.tiles_ci : 1, myshare = spread ? iy * p.tiles_ci + tci : 0;
     int bphase = 0;                                              // share of the next sub-step to be stored
     float bs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float* btab = reinterpret_cast<float*>(&smem[LDSB0]) + tid;       // BLDS: [8][NTt] floats, slot k of this thread at btab[k * NTt]
-    if (BLDS && do_bias) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) btab[k * NTt] = 0.f;
-    }
     auto lstore1 = [&](char* st, const u32x4 (&ra)[NPA], const u32x4 (&rb)[NXL]) __attribute__((always_inline)) {
         const bool mine = do_bias && bphase == myshare;          // wave-uniform
         if (++bphase == nshare) bphase = 0;
@@ -547,15 +588,10 @@ __global__ __launch_bounds__(WM * NH * 64) void conv_wgrad_row_kernel(WgK p) {
         for (int i = 0; i < NPA; ++i) {
             *reinterpret_cast<u32x4*>(st + (rra + i * RPPA) * RSA + cka * 16) = ra[i];
             if (mine) {
-                const float v[8] = {__uint_as_float(ra[i].x << 16), __uint_as_float(ra[i].x & 0xffff0000u),
-                                    __uint_as_float(ra[i].y << 16), __uint_as_float(ra[i].y & 0xffff0000u),
-                                    __uint_as_float(ra[i].z << 16), __uint_as_float(ra[i].z & 0xffff0000u),
-                                    __uint_as_float(ra[i].w << 16), __uint_as_float(ra[i].w & 0xffff0000u)};
+                float v[8];
+                bf16x8_unpack(ra[i], v);
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if constexpr (BLDS) __hip_atomic_fetch_add(btab + k * NTt, v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    else bs[k] += v[k];
-                }
+                for (int k = 0; k < 8; ++k) bs[k] += v[k];
             }
         }
 #pragma unroll
@@ -656,56 +692,18 @@ __global__ __launch_bounds__(WM * NH * 64) void conv_wgrad_row_kernel(WgK p) {
     }
     if (do_bias) {
         float* red = reinterpret_cast<float*>(&smem[0]);
-        if constexpr (!BLDS) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) red[tid * 8 + k] = bs[k];
-        }
-        __syncthreads();
-        if (tid < CPRA) {
-            for (int k = 0; k < 8; ++k) {
-                float a = 0.f;
-                for (int r = 0; r < RPPA; ++r) a += BLDS ? btab[k * NTt + r * CPRA] : red[(r * CPRA + tid) * 8 + k];
-                const int co = co0 + tid * 8 + k;
-                if (spread) p.wsb[((size_t)bz * gridDim.x + bx) * BMc + tid * 8 + k] = a;      // partial of (slice, workgroup)
-                else if (co < p.Cout && a != 0.f) atomicAdd(p.dbias + co, a);
-            }
-        }
-        __syncthreads();
+        for (int k = 0; k < 8; ++k) red[tid * 8 + k] = bs[k];
+        WG_BIAS_FINISH(CPRA, RPPA, 8, red[(r * CPRA + tid) * 8 + k], spread, gridDim.x, bx);       // partial of (slice, workgroup)
     }
     // epilogue: 32 x 32 accumulator tiles through a per-wave LDS block
     float* ep = reinterpret_cast<float*>(&smem[0]) + wave * (32 * 32);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int t = 0; t < KW; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                ep[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = acc[a][t][r];
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier();
-            const int ci = ci0 + wn * 32 + (lane & 31);
-            const int cob = co0 + wm * 64 + a * 32 + (lane >> 5);
-            const int tap = irow * KW + t;
-            if (p.ws) {
-                // partial tile of this row slice: [slice][x-block][tap of the row][BMc][BNc], plain coalesced stores
-                float* wt = p.ws + (((size_t)bz * gridDim.x + bx) * KW + t) * (size_t)(BMc * BNc) +
-                            (size_t)(wm * 64 + a * 32) * BNc + wn * 32;
-#pragma unroll 1
-                for (int j = 0; j < 16; ++j)
-                    wt[(size_t)(2 * j + (lane >> 5)) * BNc + (lane & 31)] = ep[(2 * j + (lane >> 5)) * 32 + (lane & 31)];
-            } else if (ci < p.Cin_real) {
-                float* dst = p.dw + ci * p.s_ci + tap * p.s_tap;
-#pragma unroll 1
-                for (int j = 0; j < 16; ++j) {
-                    const int co = cob + 2 * j;
-                    const float v = ep[(2 * j + (lane >> 5)) * 32 + (lane & 31)];
-                    if (co < p.Cout && v != 0.f) atomicAdd(dst + co * p.s_co, v);
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
+        for (int t = 0; t < KW; ++t)
+            WG_TILE_TAIL(acc[a][t], wm * 64 + a * 32, wn * 32, KW, t, irow * KW + t);
 }
-
 // compile-time loop (the unit index of conv_wgrad_row4_kernel must be a constant expression: it selects the register class of an
 // accumulator tile)
 template <int I, int N, typename F>
@@ -758,10 +756,8 @@ __device__ __forceinline__ void mfma_pinned(f32x16& c, const bf16x8& a, const bf
 // workspace; wgrad_fold_reduce_kernel forms dw from them.  p.H / p.W / p.M are the INPUT grid's, p.Cout = p.Cy = 4 * cout_f.
 template <int KW, int AW, int BW, int WCO, int WCI, bool RELU, int DEPTH = 2, bool FOLD = false>
 __global__ __launch_bounds__(256) void conv_wgrad_row4_kernel(WgK p) {
-    // bias column sums: eight registers.  The pinned tile with two staging sets has none left (an LDS table updated with ds_add_f32 ran
-    // such launches 2x longer: that form only stays correct, the planner does not use it): launches with a bias gradient take the pinned
-    // tile with ONE staging set (DEPTH 1, 222 + 256 registers) -- 786 k x 256 -> 256 incl. reduce / bias kernels 1050 -> 950 us against
-    // the 128 x 128 tile they took before (depth 2 is worth 6.5 % on that tile, the larger tile 18 %)
+    // bias column sums: eight registers.  The pinned tile with two staging sets has none left and keeps them in an LDS table updated
+    // with ds_add_f32: that form only stays correct, wg_choose_tile gives launches with a bias gradient DEPTH 1 (222 + 256 registers)
     constexpr bool BLDS = KW == 3 && AW * BW * KW > 16 && DEPTH >= 2;        // (5 taps: 20 tiles, four of them in VGPRs -- registers to spare; DEPTH 1: one staging set less)
     static_assert(WCO * WCI == 4, "four waves, one per SIMD");
     constexpr int NTt = 256, BMc = WCO * AW * 32, NHB = WCI * BW, BNc = NHB * 32;
@@ -926,10 +922,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_row4_kernel(WgK p) {
             char* dst = op < NPA ? st + (rra + op * RPPA) * RSA + cka * 16 : st + TA_BYTES + xdst0 + (op - NPA) * (NTt / CPX) * 64;
             if (op < NPA || XFULL || tid + (op - NPA) * NTt < XROWS * CPX) *reinterpret_cast<u32x2*>(dst + half * 8) = h2;
             if (half == 1 || op >= NPA || !mine) return;
-            const float v8[8] = {__uint_as_float(R[op].x << 16), __uint_as_float(R[op].x & 0xffff0000u),
-                                 __uint_as_float(R[op].y << 16), __uint_as_float(R[op].y & 0xffff0000u),
-                                 __uint_as_float(R[op].z << 16), __uint_as_float(R[op].z & 0xffff0000u),
-                                 __uint_as_float(R[op].w << 16), __uint_as_float(R[op].w & 0xffff0000u)};
+            float v8[8];
+            bf16x8_unpack(R[op], v8);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 if constexpr (BLDS) __hip_atomic_fetch_add(btab + k * NTt, v8[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -940,10 +934,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_row4_kernel(WgK p) {
         if (op < NPA) {
             *reinterpret_cast<u32x4*>(st + (rra + op * RPPA) * RSA + cka * 16) = R[op];
             if (mine) {                                           // (the thread's own slots: ds_add_f32, same order of additions as a register sum)
-                const float v[8] = {__uint_as_float(R[op].x << 16), __uint_as_float(R[op].x & 0xffff0000u),
-                                    __uint_as_float(R[op].y << 16), __uint_as_float(R[op].y & 0xffff0000u),
-                                    __uint_as_float(R[op].z << 16), __uint_as_float(R[op].z & 0xffff0000u),
-                                    __uint_as_float(R[op].w << 16), __uint_as_float(R[op].w & 0xffff0000u)};
+                float v[8];
+                bf16x8_unpack(R[op], v);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     if constexpr (BLDS) __hip_atomic_fetch_add(btab + k * NTt, v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1084,17 +1076,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_row4_kernel(WgK p) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) btab[k * NTt] = bs[k];
         }
-        __syncthreads();
-        if (tid < CPRA) {
-            for (int k = 0; k < 8; ++k) {
-                float a = 0.f;
-                for (int r = 0; r < RPPA; ++r) a += btab[k * NTt + r * CPRA];
-                const int co = co0 + tid * 8 + k;
-                if (spread) p.wsb[((size_t)bz * gridDim.x + bx) * BMc + tid * 8 + k] = a;
-                else if (co < p.Cout && a != 0.f) atomicAdd(p.dbias + co, a);
-            }
-        }
-        __syncthreads();
+        WG_BIAS_FINISH(CPRA, RPPA, 8, btab[k * NTt + r * CPRA], spread, gridDim.x, bx);
     }
     float* ep = reinterpret_cast<float*>(&smem[0]) + wave * (32 * 32);
 #pragma unroll
@@ -1102,36 +1084,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_row4_kernel(WgK p) {
 #pragma unroll
         for (int b = 0; b < BW; ++b)
 #pragma unroll
-            for (int t = 0; t < KW; ++t) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    ep[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = acc[a][b][t][r];
-                __builtin_amdgcn_s_waitcnt(0xc07f);
-                __builtin_amdgcn_wave_barrier();
-                const int ci = ci0 + (wn * BW + b) * 32 + (lane & 31);
-                const int cob = co0 + (wm * AW + a) * 32 + (lane >> 5);
-                const int tap = irow * KW + t;
-                if (p.ws) {
-                    float* wt = p.ws + (((size_t)bz * gridDim.x + bx) * KW + t) * (size_t)(BMc * BNc) +
-                                (size_t)((wm * AW + a) * 32) * BNc + (wn * BW + b) * 32;
-#pragma unroll 1
-                    for (int j = 0; j < 16; ++j)
-                        wt[(size_t)(2 * j + (lane >> 5)) * BNc + (lane & 31)] = ep[(2 * j + (lane >> 5)) * 32 + (lane & 31)];
-                } else if (ci < p.Cin_real) {
-                    float* dst = p.dw + ci * p.s_ci + tap * p.s_tap;
-#pragma unroll 1
-                    for (int j = 0; j < 16; ++j) {
-                        const int co = cob + 2 * j;
-                        const float v = ep[(2 * j + (lane >> 5)) * 32 + (lane & 31)];
-                        if (co < p.Cout && v != 0.f) atomicAdd(dst + co * p.s_co, v);
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
+            for (int t = 0; t < KW; ++t)
+                WG_TILE_TAIL(acc[a][b][t], (wm * AW + a) * 32, (wn * BW + b) * 32, KW, t, irow * KW + t);
 }
-
-// reduction of the row kernel's partial tiles: dw[co][ci][iy*KW + t] += sum over slices
-struct WgRowRedK { const float* ws; float* dw; int nslice, gx, tiles_co, tiles_ci, BMc, BNc, KW, Cout, Cin_real; long long s_co, s_ci, s_tap; int overwrite; };
+#undef WG_BIAS_FINISH
+#undef WG_TILE_TAIL
+// ============================================================================ fixed-order reduce kernels of the slice workspace
 // sum over the slices of four consecutive partial-tile elements (16-byte loads, four slices requested before the first addition;
 // slice order kept): the reduce kernels stream the whole workspace once and were running at 2.5 TB/s with scalar loads
 __device__ __forceinline__ f32x4 slice_sum4(const float* ws, int nslice, size_t stride, size_t off) {
@@ -1147,60 +1105,71 @@ __device__ __forceinline__ f32x4 slice_sum4(const float* ws, int nslice, size_t 
     for (; z < nslice; ++z) a += *reinterpret_cast<const f32x4*>(ws + (size_t)z * stride + off);
     return a;
 }
+// store tail of the tile reduces: the sums of four consecutive in-channels (from ci on) replace or join dw
+__device__ __forceinline__ void wg_store4(float* d, long long s_ci, int ci, int Cin_real, const f32x4& a, int overwrite) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (ci + j < Cin_real) d[j * s_ci] = overwrite ? a[j] : d[j * s_ci] + a[j];
+}
+// Fixed-order sum of item(0 .. nitem - 1) for each of the block's 32 channels (c = threadIdx.x & 31) by 32 partial lanes
+// (l = threadIdx.x >> 5): lane l adds items l, l + 32, ... eight loads at a time (a few thousand partials per channel on the large
+// shapes: as a serial chain on 8 lanes this took ~250 us), then the 32 lane sums are added in lane order.  The sum is returned to lane 0.
+template <typename F>
+__device__ __forceinline__ float block_sum_32x32(int nitem, F&& item) {
+    __shared__ float red[32][33];
+    const int c = threadIdx.x & 31, l = threadIdx.x >> 5;
+    float a = 0.f;
+    for (int i = l; i < nitem; i += 32 * 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = i + 32 * u < nitem ? item(i + 32 * u) : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) a += v[u];
+    }
+    red[l][c] = a;
+    __syncthreads();
+    if (l == 0)
+        for (int j = 1; j < 32; ++j) a += red[j][c];
+    return a;
+}
 
+// Second phase of the workspace path: dw[co][ci][irow * KW + t] (+)= sum over row slices of the partial tiles, for the filter-row
+// kernels (irow = filter row, KW taps per tile) and the one-tap kernel (KW = 1: irow is the tap)
+struct WgRowRedK { const float* ws; float* dw; int nslice, gx, tiles_co, tiles_ci, BMc, BNc, KW, Cout, Cin_real; long long s_co, s_ci, s_tap; int overwrite; };
 __global__ void wgrad_row_reduce_kernel(WgRowRedK p) {
-    const int tile_elems = p.KW * p.BMc * p.BNc;
+    const int tile = p.BMc * p.BNc, tile_elems = p.KW * tile;
     const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;      // 4 consecutive in-channels per thread
     if (i >= (long long)p.gx * tile_elems) return;
+    // decode bx exactly like the kernels: irow = bx / (tiles_co * tiles_ci), rem -> (tco, tci)
     const int bx = (int)(i / tile_elems), e = (int)(i - (long long)bx * tile_elems);
-    const int t = e / (p.BMc * p.BNc), e2 = e - t * (p.BMc * p.BNc);
+    const int t = e / tile, e2 = e - t * tile;
     const int r = e2 / p.BNc, c = e2 - r * p.BNc;
     const int tiles = p.tiles_co * p.tiles_ci;
     const int iy = bx / tiles, rem = bx - iy * tiles;
     const int tco = rem / p.tiles_ci, tci = rem - tco * p.tiles_ci;
     const int co = tco * p.BMc + r, ci = tci * p.BNc + c;
     if (co >= p.Cout || ci >= p.Cin_real) return;
-    const f32x4 a = slice_sum4(p.ws, p.nslice, (size_t)p.gx * tile_elems, (size_t)bx * tile_elems + e);
-    float* d = p.dw + co * p.s_co + ci * p.s_ci + (iy * p.KW + t) * p.s_tap;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (ci + j < p.Cin_real) d[j * p.s_ci] = p.overwrite ? a[j] : d[j * p.s_ci] + a[j];
+    const f32x4 a = slice_sum4(p.ws, p.nslice, ws_slice_stride(p.gx, p.KW, tile), ws_tile_off(0, p.gx, bx, p.KW, t, tile) + e2);
+    wg_store4(p.dw + co * p.s_co + ci * p.s_ci + (iy * p.KW + t) * p.s_tap, p.s_ci, ci, p.Cin_real, a, p.overwrite);
 }
 
-// bias gradient of the row kernel's workspace path: dbias[co] += sum over (slice, filter row of the centre time slab, ci tile) of the
-// partial column sums, in a fixed order (block = 32 channels x 8 partial lanes)
+// bias gradient of the row kernels' workspace path: dbias[co] += sum over (slice, filter row of the centre time slab, ci tile) of the
+// partial column sums, in a fixed order (block_sum_32x32)
 struct WgBiasRedK { const float* wsb; float* dbias; int nslice, gx, tiles_co, tiles_ci, KW, kt, BMc, Cout; };
 __global__ __launch_bounds__(1024) void wgrad_row_bias_reduce_kernel(WgBiasRedK p) {
-    // block = 32 channels x 32 partial lanes; a lane walks its items eight loads at a time (a few thousand partials per channel on
-    // the large shapes: as a serial chain on 8 lanes this kernel took ~250 us)
-    __shared__ float red[32][33];
     const int gpt = p.BMc / 32;
     const int tco = blockIdx.x / gpt, cg = blockIdx.x - tco * gpt;
-    const int c = threadIdx.x & 31, l = threadIdx.x >> 5;
-    const int tiles = p.tiles_co * p.tiles_ci, per = p.KW * p.tiles_ci, nitem = p.nslice * per;
+    const int c = threadIdx.x & 31;
+    const int tiles = p.tiles_co * p.tiles_ci, per = p.KW * p.tiles_ci;
     const int irow0 = (p.kt >> 1) * p.KW;
-    auto item = [&](int i) __attribute__((always_inline)) -> float {
-        if (i >= nitem) return 0.f;
+    const float a = block_sum_32x32(p.nslice * per, [&](int i) __attribute__((always_inline)) -> float {
         const int bz = i / per, r = i - bz * per;
         const int iy = r / p.tiles_ci, tci = r - iy * p.tiles_ci;
         const int bx = (irow0 + iy) * tiles + tco * p.tiles_ci + tci;
-        return p.wsb[((size_t)bz * p.gx + bx) * p.BMc + cg * 32 + c];
-    };
-    float a = 0.f;
-    for (int i = l; i < nitem; i += 32 * 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = item(i + 32 * u);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) a += v[u];
-    }
-    red[l][c] = a;
-    __syncthreads();
-    if (l == 0) {
-        for (int j = 1; j < 32; ++j) a += red[j][c];
-        const int co = tco * p.BMc + cg * 32 + c;
-        if (co < p.Cout) p.dbias[co] += a;
-    }
+        return p.wsb[ws_bias_off(bz, p.gx, bx, p.BMc) + cg * 32 + c];
+    });
+    const int co = tco * p.BMc + cg * 32 + c;
+    if (threadIdx.x < 32 && co < p.Cout) p.dbias[co] += a;
 }
 
 // bias gradient of the one-tap kernel's workspace path: dbias[co] += sum over the row slices.  Block = 64 channels x 16 slice lanes:
@@ -1213,7 +1182,7 @@ __global__ __launch_bounds__(1024) void wgrad_bias_reduce_kernel(const float* ws
     if (co < Cout) {
         const int tco = co / BMc, c = co - tco * BMc;
 #pragma unroll 4
-        for (int z = q; z < nslice; z += 16) a += wsb[((size_t)z * tiles_co + tco) * BMc + c];
+        for (int z = q; z < nslice; z += 16) a += wsb[ws_bias_off(z, tiles_co, tco, BMc) + c];
     }
     red[q][col] = a;
     __syncthreads();
@@ -1223,27 +1192,6 @@ __global__ __launch_bounds__(1024) void wgrad_bias_reduce_kernel(const float* ws
         for (int i = 1; i < 16; ++i) t += red[i][col];
         dbias[co] += t;
     }
-}
-
-// Second phase of the workspace path: dw[co][ci][tap] += sum over row slices of the partial tiles.
-struct WgRedK { const float* ws; float* dw; int nslice, gx, gx_per_tap, tiles_ci, BMc, BNc, Cout, Cin_real; long long s_co, s_ci, s_tap; int overwrite; };
-__global__ void wgrad_reduce_kernel(WgRedK p) {
-    const int tile_elems = p.BMc * p.BNc;
-    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= (long long)p.gx * tile_elems) return;
-    const int bx = (int)(i / tile_elems), e = (int)(i - (long long)bx * tile_elems);
-    const int r = e / p.BNc, c = e - r * p.BNc;
-    // decode bx exactly like the kernel: tap = bx / (tiles_co*tiles_ci), rem -> (tco, tci)
-    const int per_tap = p.gx_per_tap;
-    const int tap = bx / per_tap, rem = bx - tap * per_tap;
-    const int tco = rem / p.tiles_ci, tci = rem - tco * p.tiles_ci;
-    const int co = tco * p.BMc + r, ci = tci * p.BNc + c;
-    if (co >= p.Cout || ci >= p.Cin_real) return;
-    const f32x4 a = slice_sum4(p.ws, p.nslice, (size_t)p.gx * tile_elems, (size_t)bx * tile_elems + e);
-    float* d = p.dw + co * p.s_co + ci * p.s_ci + tap * p.s_tap;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (ci + j < p.Cin_real) d[j * p.s_ci] = p.overwrite ? a[j] : d[j * p.s_ci] + a[j];
 }
 
 // Reduction of the folded form (conv_wgrad_row4_kernel<.., FOLD>): dw[co][ci][ky][kx] (+)= sum over the four phases (a, b), in that
@@ -1266,220 +1214,309 @@ __global__ void wgrad_fold_reduce_kernel(WgFoldRedK p) {
         const int irow = sy - a + 1, t = sx + 1;
         const int cop = ph * p.Cout + co;
         const int bx = irow * tiles + (cop >> 7) * p.tiles_ci + (ci >> 7);
-        const size_t off = ((size_t)bx * 3 + t) * (128 * 128) + (size_t)(cop & 127) * 128 + (ci & 127);
-        acc += slice_sum4(p.ws, p.nslice, (size_t)p.gx * 3 * (128 * 128), off);
+        const size_t off = ws_tile_off(0, p.gx, bx, 3, t, 128 * 128) + (size_t)(cop & 127) * 128 + (ci & 127);
+        acc += slice_sum4(p.ws, p.nslice, ws_slice_stride(p.gx, 3, 128 * 128), off);
     }
-    float* d = p.dw + co * p.s_co + ci * p.s_ci + tap * p.s_tap;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (ci + j < p.Cin_real) d[j * p.s_ci] = p.overwrite ? acc[j] : d[j * p.s_ci] + acc[j];
+    wg_store4(p.dw + co * p.s_co + ci * p.s_ci + tap * p.s_tap, p.s_ci, ci, p.Cin_real, acc, p.overwrite);
 }
 // its bias gradient: dbias[co] += sum over (phase, slice, filter row, ci tile) of the workgroups' partial column sums, fixed order
-// (block = 32 channels x 32 partial lanes, as wgrad_row_bias_reduce_kernel)
+// (block_sum_32x32, as wgrad_row_bias_reduce_kernel)
 struct WgFoldBiasK { const float* wsb; float* dbias; int nslice, gx, tiles_ci, Cout; };
 __global__ __launch_bounds__(1024) void wgrad_fold_bias_reduce_kernel(WgFoldBiasK p) {
-    __shared__ float red[32][33];
-    const int c = threadIdx.x & 31, l = threadIdx.x >> 5, co = blockIdx.x * 32 + c;
-    const int tiles = (4 * p.Cout / 128) * p.tiles_ci, per = 2 * p.tiles_ci, nitem = 4 * p.nslice * per;
-    auto item = [&](int i) __attribute__((always_inline)) -> float {
-        if (i >= nitem || co >= p.Cout) return 0.f;
+    const int co = blockIdx.x * 32 + (threadIdx.x & 31);
+    const int tiles = (4 * p.Cout / 128) * p.tiles_ci, per = 2 * p.tiles_ci;
+    const float a = block_sum_32x32(4 * p.nslice * per, [&](int i) __attribute__((always_inline)) -> float {
+        if (co >= p.Cout) return 0.f;
         const int ph = i / (p.nslice * per), r0 = i - ph * (p.nslice * per);
         const int bz = r0 / per, r = r0 - bz * per;
         const int irow = r / p.tiles_ci, tci = r - irow * p.tiles_ci;
         const int cop = ph * p.Cout + co;
         const int bx = irow * tiles + (cop >> 7) * p.tiles_ci + tci;
-        return p.wsb[((size_t)bz * p.gx + bx) * 128 + (cop & 127)];
-    };
-    float a = 0.f;
-    for (int i = l; i < nitem; i += 32 * 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = item(i + 32 * u);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) a += v[u];
-    }
-    red[l][c] = a;
-    __syncthreads();
-    if (l == 0) {
-        for (int j = 1; j < 32; ++j) a += red[j][c];
-        if (co < p.Cout) p.dbias[co] += a;
-    }
+        return p.wsb[ws_bias_off(bz, p.gx, bx, 128) + (cop & 127)];
+    });
+    if (threadIdx.x < 32 && co < p.Cout) p.dbias[co] += a;
 }
+
+// ============================================================================ planner
+// A request becomes ONE WgPlan in three steps: wg_fill_request (validate, fill the kernel arguments), wg_choose_tile (kernel family,
+// channel tile, staging depth) and wg_choose_split (row slices, grid); wgrad_plan then fixes the slice-workspace layout.
+// Tuning constants, each the winner of a measured sweep.  Workgroups aimed at per launch:
+// one-tap kernel, ~16 per CU.  Swept on the full step with the workspace reduction (ms of wgrad per step), (target, WG_MINROWS):
+// (1024,8192) 292, (1536,8192) 267, (3072,4096) 247, (4096,4096) 243, (6144,4096) 242, (8192,2048) 252; re-swept with whole-round
+// grids: 4096 185.6, 2048 183.2, 1024 183.5 ms
+constexpr long long WG_TGT_TAP = 2048, WG_MINROWS = 4096;      // (WG_MINROWS: rows of reduction every workgroup keeps)
+// 8-wave filter-row tiles (rounds 1-3, swept with whole-round grids: 1024 187.7, 1536 185.1, 2048 190.8, 3072 192.2 ms of weight gradients.
+// End of round 4 -- the chain's kernels no longer leave the side stream the CUs they used to -- fewer, longer slices win on the STEP:
+// 256 503.4 / 503.8, 384 498.1 / 498.1, 512 495.6 / 495.7, 768 497.7 / 498.5, 1024 498.4 / 497.3, 1536 500.4 / 500.3, 3072 501.3 ms, one box)
+constexpr long long WG_TGT_ROW = 512;
+// 64-channel filter-row tile: 2-wave workgroups, three per CU -> one round of 768 (tools/conv_microbench.py wgrad 30,32 incl. reduce +
+// bias kernels, interleaved: 512 1736 / 314 us, 768 1537 / 264, 1536 1597 / 322, 3072 1648 / 326)
+constexpr long long WG_TGT_ROW64 = 768;
+// one wave per SIMD (one workgroup per CU at a time): ONE round of 256 workgroups -- step at C2, interleaved on one box: one round
+// 451.3 / 451.8 ms, two 452.1 / 452.3, three 454.5 / 454.2 (half the slice workspace per halving) -- two rounds beyond 6 M rows
+// (configs[3], 4x the rows per launch: one round 1802 ms, two 1739)
+constexpr long long WG_TGT_ROW4 = 256, WG_TGT_ROW4_LARGE = 512, WG_ROW4_LARGE_M = 6ll << 20;
+// ... and it needs a round of workgroups with >= 4096 rows each (256 x 256 channels on 48 k rows ran 172 us against 101 on the 8-wave tile)
+constexpr long long WG_ROW4_MIN_WGS = 224, WG_ROW4_WG_ROWS = 4096;
+constexpr long long WG_CUS = 256;                 // workgroups of one round at one workgroup per CU
+
+enum WgFamily { WG_TAP = 0, WG_ROW = 1, WG_ROW4 = 2 };      // one tap per workgroup / 8-wave filter row / filter row, one wave per SIMD
+
+struct WgPlan {
+    int rc;                                      // DVD_OK, or why there is no plan
+    WgK p;
+    dim3 grid;                                   // (workgroups of a slice, 1, slices)
+    WgFamily family;
+    int bm, bn;                                  // channel tile: out-channels x in-channels
+    int kw_tile, esz;                            // taps per partial tile (kw, one-tap kernel: 1); bytes per element of x / dy
+    int depth, fold;                             // WG_ROW4: staging register sets (0 otherwise); the folded form of an x2-upsampled layer
+    long long msplit;                            // row slices
+    long long tile_floats, bias_floats;          // slice workspace: partial tiles, then bias partials (ws_tile_off / ws_bias_off)
+    long long total() const { return tile_floats + bias_floats; }
+    // workgroups of a slice: one per channel tile and tap, or per filter row (folded: two rows)
+    long long base() const { return (long long)p.tiles_co * p.tiles_ci * (family == WG_TAP ? p.kt * p.kh * p.kw : fold ? 2 : p.kt * p.kh); }
+};
 
 }  // namespace
 
-// Validates a weight-gradient request and derives tile shape, grid and row split.
-// mode: 0 = one tap per workgroup (conv_wgrad_kernel), 1 = one filter row per workgroup (conv_wgrad_row_kernel; ta = WM)
-// fold: `d` is the folded request of an x2-upsampled 3 x 3 layer (wgrad_plan below): only the one-wave-per-SIMD 128 x 128 tile serves it
-static int wgrad_plan1(const dvd_wgrad_desc* d, WgK& p, dim3& grid, int& ta, int& tb, long long& msplit, int& mode, bool fold) {
+// Step 1: validate the request and fill the kernel arguments that do not depend on the tile.
+static int wg_fill_request(const dvd_wgrad_desc* d, WgPlan& pl) {
     if (!d || !d->x || !d->dy || !d->dw) return DVD_E_ARG;
     int logH = ilog2_exact(d->H), logW = ilog2_exact(d->W);
-    const bool pow2 = logH >= 0 && logW >= 0;
-    if (!pow2) logH = logW = -1;           // division-based indexing, one-tap kernel only
+    if (logH < 0 || logW < 0) logH = logW = -1;           // division-based indexing, one-tap kernel only
     if (d->up2 && ((d->H | d->W) & 1)) return DVD_E_SHAPE;
     if ((d->C & 7) || (d->ldx & 7) || (d->Cy & 7) || (d->ldy & 7) || !(d->kt & d->kh & d->kw & 1)) return DVD_E_SHAPE;
     if (d->Cout > d->Cy || d->Cin_real > d->C) return DVD_E_ARG;
     if (d->dtype != DVD_BF16 && d->dtype != DVD_F32) return DVD_E_ARG;
     const long long M = (long long)d->frames * d->T * d->H * d->W;
     if (M >= (1ll << 31) - 64) return DVD_E_SHAPE;
+    WgK& p = pl.p;
     p.x = (const char*)d->x; p.dy = (const char*)d->dy; p.dw = d->dw;
     p.M = (int)M; p.C = d->C; p.ldx = d->ldx; p.Cin_real = d->Cin_real; p.Cout = d->Cout; p.Cy = d->Cy; p.ldy = d->ldy;
     p.T = d->T; p.H = d->H; p.W = d->W; p.logH = logH; p.logW = logW;
     p.Hin = d->up2 ? d->H / 2 : d->H; p.Win = d->up2 ? d->W / 2 : d->W;
     p.kt = d->kt; p.kh = d->kh; p.kw = d->kw; p.up2 = d->up2; p.relu_in = d->relu_in;
-    // bf16: 256-wide tile along whichever channel axis is long enough (2x the MFMAs per barrier)
-    ta = 2; tb = 2;
-    if (d->dtype == DVD_BF16) {
-        if (d->Cout >= 192) ta = 4;
-        else if (d->Cin_real >= 192) tb = 4;
+    p.s_co = d->s_co; p.s_ci = d->s_ci; p.s_tap = d->s_tap; p.dbias = d->dbias; p.ws = nullptr; p.wsb = nullptr;
+    p.xcd_remap = 1;
+    p.fold = 0; p.cout_f = d->Cout;
+    pl.esz = d->dtype == DVD_BF16 ? 2 : 4;
+    const size_t rows_in = (size_t)d->frames * d->T * p.Hin * p.Win;
+    p.x_bytes = ((rows_in - 1) * (size_t)d->ldx + d->C) * pl.esz;
+    p.dy_bytes = (((size_t)M - 1) * (size_t)d->ldy + d->Cy) * pl.esz;
+    p.maxshift = ((d->kt >> 1) * d->H + (d->kh >> 1)) * d->W + (d->kw >> 1);
+    return DVD_OK;
+}
+
+// Step 2: the kernel family, its channel tile and (one wave per SIMD) its staging depth.
+// fold: `d` is the folded request of an x2-upsampled 3 x 3 layer (wgrad_plan): only the one-wave-per-SIMD 128 x 128 tile serves it.
+static int wg_choose_tile(const dvd_wgrad_desc* d, bool fold, WgPlan& pl) {
+    const WgK& p = pl.p;
+    const bool bf16 = d->dtype == DVD_BF16, pow2 = p.logW >= 0;
+    // one-tap kernel.  bf16: 256-wide tile along whichever channel axis is long enough (2x the MFMAs per barrier)
+    pl.family = WG_TAP; pl.bm = 128; pl.bn = 128; pl.depth = 0; pl.fold = fold;
+    if (bf16) {
+        if (d->Cout >= 192) pl.bm = 256;
+        else if (d->Cin_real >= 192) pl.bn = 256;
     }
-    mode = (pow2 && d->dtype == DVD_BF16 && d->kh == d->kw && (d->kw == 3 || d->kw == 5) && (!d->up2 || (d->kw == 3 && d->kt == 1)) &&
-            ((d->W >= 8 && (d->H * d->W) % 32 == 0) ||
-             // 4 x 4 frames (round 4): a 32-pixel step = two whole frames
-             (d->W == 4 && d->H == 4 && d->kt == 1 && d->T == 1 && !d->up2 && (d->frames & 1) == 0))) ? 1 : 0;
-    if (mode == 1) {   // 64 channels for thin outputs, else 256 or 128, whichever pads Cout less (256 on a tie)
+    const bool row = pow2 && bf16 && d->kh == d->kw && (d->kw == 3 || d->kw == 5) && (!d->up2 || (d->kw == 3 && d->kt == 1)) &&
+                     ((d->W >= 8 && (d->H * d->W) % 32 == 0) ||
+                      // 4 x 4 frames (round 4): a 32-pixel step = two whole frames
+                      (d->W == 4 && d->H == 4 && d->kt == 1 && d->T == 1 && !d->up2 && (d->frames & 1) == 0));
+    if (row) {   // 64 channels for thin outputs, else 256 or 128, whichever pads Cout less (256 on a tie)
         const int w4 = (d->Cout + 255) / 256 * 256, w2 = (d->Cout + 127) / 128 * 128;
-        ta = d->Cout <= 64 ? 1 : (w4 <= w2 ? 4 : 2); tb = 1;
+        pl.family = WG_ROW;
+        pl.bm = d->Cout <= 64 ? 64 : (w4 <= w2 ? 256 : 128); pl.bn = 64;
         // 128-channel output tile, 5 taps: take 128 input channels too (one 8-wave workgroup per CU whose halves stagger their
         // loads, like the 256-channel tile) when that pads Cin no further: 1.20 -> 1.33 PF/s on 3.1 M x 256 -> 384; with 3 taps
         // the two 4-wave workgroups per CU of the 64-channel form stay 3 % ahead
         const bool ci128 = (d->Cin_real + 127) / 128 * 128 == (d->Cin_real + 63) / 64 * 64;      // 128-channel input tiles pad no further
-        if (ta == 2 && d->kw == 5 && !d->up2 && ci128) tb = 2;
-#ifndef DVD_WG_ROW4                    // 0 = 8-wave tiles only, 1 = the 128 x 128 one-wave-per-SIMD 3-tap tile only, 2 = + the pinned 256 x 128 tile, 3 = + 5 taps
-#define DVD_WG_ROW4 3
-#endif
-#ifndef DVD_ROW4_DEPTH                 // staging depth of the 128 x 128 one-wave-per-SIMD tile (experiment knob)
-#define DVD_ROW4_DEPTH 2
-#endif
-        // round 6: one wave per SIMD with the whole register file (conv_wgrad_row4_kernel), mode 2.
-        //   3 taps: 256 x 128 channels (pinned, 24 tiles; with a bias gradient: one staging set) or 128 x 128
+        if (pl.bm == 128 && d->kw == 5 && !d->up2 && ci128) pl.bn = 128;
+        // round 6: one wave per SIMD with the whole register file (conv_wgrad_row4_kernel).
+        //   3 taps: 256 x 128 channels (pinned, 24 tiles) or 128 x 128 (also the folded form)
         //   5 taps: 256 x 64 or 128 x 128 (20 tiles)
-        // Needs a round of workgroups with >= 4096 rows each (256 x 256 channels on 48 k rows ran 172 us against 101 on the 8-wave tile);
-        // a caller-forced split (msplit > 0: tests) takes the tile whatever the size.
-        if (DVD_WG_ROW4 && !d->up2 && ta >= 2 && (d->kw == 3 ? ci128 : (DVD_WG_ROW4 >= 3 && (ta == 4 || ci128)))) {
-            int t4 = ta, b4 = 2;
-#ifndef DVD_WG_PIN_BIAS                // 1 = launches with a bias gradient take the pinned tile too, with ONE staging set (DEPTH 1) so that the column sums have registers
-#define DVD_WG_PIN_BIAS 1
-#endif
-            if (d->kw == 3) { if (DVD_WG_ROW4 == 1 || (d->dbias && !DVD_WG_PIN_BIAS) || fold) t4 = 2; }
-            else if (ta == 4) b4 = 1;
-            const long long wgs = (long long)((d->Cout + t4 * 64 - 1) / (t4 * 64)) * ((d->Cin_real + b4 * 64 - 1) / (b4 * 64)) * d->kt * d->kh * (M / 4096);
-            if (wgs >= 224 || d->msplit > 0) { mode = 2; tb = b4; ta = t4; }
-        }
-    }
-    if (fold && mode != 2) return DVD_E_SHAPE;
-    const int nrow = fold ? 2 : d->kt * d->kh;                   // filter rows per (channel tile, slice) of the filter-row kernels
-    p.tiles_co = (d->Cout + ta * 64 - 1) / (ta * 64); p.tiles_ci = (d->Cin_real + tb * 64 - 1) / (tb * 64);
-    p.s_co = d->s_co; p.s_ci = d->s_ci; p.s_tap = d->s_tap; p.dbias = d->dbias; p.ws = nullptr;
-    p.xcd_remap = 1;
-    {
-        const size_t esz = d->dtype == DVD_BF16 ? 2 : 4;
-        const size_t rows_in = (size_t)d->frames * d->T * p.Hin * p.Win;
-        p.x_bytes = ((rows_in - 1) * (size_t)d->ldx + d->C) * esz;
-        p.dy_bytes = (((size_t)M - 1) * (size_t)d->ldy + d->Cy) * esz;
-        p.maxshift = ((d->kt >> 1) * d->H + (d->kh >> 1)) * d->W + (d->kw >> 1);
-    }
-    const int ntaps = d->kt * d->kh * d->kw;
-    msplit = d->msplit;
-    if (msplit < 1) {   // auto: ~16 workgroups per CU, every workgroup keeping >= 4k rows of reduction.  Swept on the
-                        // full step with the workspace reduction (ms of wgrad per step): (1024,8192) 292,
-                        // (1536,8192) 267, (3072,4096) 247, (4096,4096) 243, (6144,4096) 242, (8192,2048) 252
-        constexpr long long tgt = 2048;   // re-swept with whole-round grids: 4096 185.6, 2048 183.2, 1024 183.5 ms
-        constexpr long long minrows = 4096;
-        // (rounds 1-3, swept with whole-round grids: 1024 187.7, 1536 185.1, 2048 190.8, 3072 192.2 ms of weight gradients.  End of round 4 -- the
-        //  chain's kernels no longer leave the side stream the CUs they used to -- fewer, longer slices win on the STEP: 256 503.4 / 503.8,
-        //  384 498.1 / 498.1, 512 495.6 / 495.7, 768 497.7 / 498.5, 1024 498.4 / 497.3, 1536 500.4 / 500.3, 3072 501.3 ms, one box)
-        constexpr long long tgt_row = 512;
-        const long long base = (long long)p.tiles_co * p.tiles_ci * (mode >= 1 ? nrow : ntaps);
-        // one-wave-per-SIMD tiles (one workgroup per CU at a time): ONE round of 256 workgroups -- step at C2, interleaved on one box:
-        // one round 451.3 / 451.8 ms, two 452.1 / 452.3, three 454.5 / 454.2 (half the slice workspace per halving) -- two rounds
-        // beyond 6 M rows (configs[3], 4x the rows per launch: one round 1802 ms, two 1739)
-        const long long tgt4 = M > (6ll << 20) ? 512 : 256;
-#ifndef DVD_WG_TGT1                    // 64-channel output tile: 2-wave workgroups, three per CU -> one round of 768 (tools/conv_microbench.py wgrad
-#define DVD_WG_TGT1 768                // 30,32 incl. reduce + bias kernels, interleaved: 512 1736 / 314 us, 768 1537 / 264, 1536 1597 / 322, 3072 1648 / 326)
-#endif
-        const long long tgt1 = (mode == 1 && ta == 1) ? (long long)DVD_WG_TGT1 : tgt_row;
-        msplit = ((mode == 2 ? tgt4 : mode == 1 ? tgt1 : tgt) + base - 1) / base;
-        long long cap = M / minrows > 0 ? M / minrows : 1;
-        if (ntaps == 1 && cap * base < 256) {
-            // short 1 x 1 layers (shortcut and attention projections on <= 16-pixel maps): 16 workgroups of 4096 rows each took
-            // 110-150 us for 4 GFLOP -- slices down to 256 rows until every CU has a workgroup (round 5)
-            const long long want = (256 + base - 1) / base, cap2 = M / 256;
-            cap = cap2 < want ? (cap2 > cap ? cap2 : cap) : want;
-        }
-        if (msplit > cap) msplit = cap;
-        // whole rounds: the workgroups run `conc` at a time (register / LDS limited); a grid a few workgroups over a
-        // multiple of that pays a full extra round (20 x 103 = 2060 workgroups = 8.05 rounds of 256 -> 9 rounds)
-        const long long conc = 256ll * ((mode >= 1 && (ta == 4 || tb == 2)) ? 1 : (mode == 1 && ta == 1 && DVD_WG_TGT1 > 512) ? 3 : 2);
-        if (base * msplit > conc) {
-            const long long rounds = (base * msplit + conc / 2) / conc;           // nearest
-            long long ms2 = rounds * conc / base;
-            if (ms2 >= 1 && ms2 <= cap) msplit = ms2;
-        }
-    }
-    long long rows = (M + msplit - 1) / msplit;
-    {   // a workgroup's row slice is addressed with 32-bit byte offsets
-        const long long ldy_eff = fold ? 4ll * d->ldy : d->ldy;     // (folded: a slice of input pixels spans four times as many rows of dy)
-        const long long ldmax = (d->ldx > ldy_eff ? d->ldx : ldy_eff) * (d->dtype == DVD_BF16 ? 2ll : 4ll);
-        const long long cap = (1ll << 31) / ldmax;
-        if (rows > cap) rows = cap;
-    }
-    rows = (rows + 31) / 32 * 32;
-    if (rows < 32) rows = 32;
-    msplit = (M + rows - 1) / rows;
-    if (mode == 2 && d->msplit < 1) {
-        // the 32-bit offset cap can undo the whole-round rounding above (configs[3]: 3.1 M x 512 -> 512 behind a 1536-wide dy: 5 slices x 80
-        // workgroups = 1.56 rounds of one workgroup per CU): fill the last round
-        const long long base = (long long)p.tiles_co * p.tiles_ci * nrow, wg = base * msplit;
-        if (wg > 256 && wg % 256 > 0 && wg % 256 < 192) {
-            const long long ms2 = ((wg + 255) / 256 * 256) / base;
-            if (ms2 > msplit && M / ms2 >= 2048) {
-                rows = ((M + ms2 - 1) / ms2 + 31) / 32 * 32;
-                msplit = (M + rows - 1) / rows;
+        // Needs WG_ROW4_MIN_WGS workgroups; a caller-forced split (msplit > 0: tests) takes the tile whatever the size.
+        if (!d->up2 && pl.bm >= 128 && (d->kw == 3 ? ci128 : (pl.bm == 256 || ci128))) {
+            int bm4 = pl.bm, bn4 = 128;
+            if (d->kw == 3) { if (fold) bm4 = 128; }
+            else if (pl.bm == 256) bn4 = 64;
+            const long long wgs = (long long)((d->Cout + bm4 - 1) / bm4) * ((d->Cin_real + bn4 - 1) / bn4) * d->kt * d->kh * (p.M / WG_ROW4_WG_ROWS);
+            if (wgs >= WG_ROW4_MIN_WGS || d->msplit > 0) {
+                pl.family = WG_ROW4; pl.bm = bm4; pl.bn = bn4;
+                // Staging depth 2, except: the pinned 256 x 128 tile with two staging sets has no registers left for the eight bias column
+                // sums (an LDS table updated with ds_add_f32 ran such launches 2x longer), so launches with a bias gradient take it with ONE
+                // staging set -- 786 k x 256 -> 256 incl. reduce / bias kernels 1050 -> 950 us against the 128 x 128 tile they took before
+                // (depth 2 is worth 6.5 % on that tile, the larger tile 18 %)
+                pl.depth = (d->kw == 3 && bm4 == 256 && d->dbias) ? 1 : 2;
             }
         }
     }
-    p.rows_per_split = (int)rows;
-    grid = dim3(p.tiles_co * p.tiles_ci * (mode >= 1 ? nrow : ntaps), 1, (unsigned)msplit);
-    p.fold = 0; p.cout_f = d->Cout;
+    if (fold && pl.family != WG_ROW4) return DVD_E_SHAPE;
+    pl.p.tiles_co = (d->Cout + pl.bm - 1) / pl.bm; pl.p.tiles_ci = (d->Cin_real + pl.bn - 1) / pl.bn;
     return DVD_OK;
 }
 
-// A 3 x 3 layer over a nearest-x2 upsampled input is planned on the input grid when the folded form applies (see
-// conv_wgrad_row4_kernel<.., FOLD>): whole 64-channel blocks of Cout, 128-wide input-channel tiles, a slice workspace (`may_fold`:
-// the caller supplied one, or is asking for its size) and enough rows for the one-wave-per-SIMD tile.
-static int wgrad_plan(const dvd_wgrad_desc* d, WgK& p, dim3& grid, int& ta, int& tb, long long& msplit, int& mode, bool may_fold) {
-#ifndef DVD_WG_FOLD
-#define DVD_WG_FOLD 1
-#endif
-    if (DVD_WG_FOLD && may_fold && d && d->up2 && d->dtype == DVD_BF16 && d->kt == 1 && d->kh == 3 && d->kw == 3 && d->T == 1 &&
+// Step 3: the row split.  A caller's msplit is taken as it is (only the 32-bit offset cap applies); the automatic split is a target
+// and four corrections.
+static long long wg_split_target(const WgPlan& pl) {
+    const long long tgt = pl.family == WG_ROW4 ? (pl.p.M > WG_ROW4_LARGE_M ? WG_TGT_ROW4_LARGE : WG_TGT_ROW4)
+                        : pl.family == WG_ROW  ? (pl.bm == 64 ? WG_TGT_ROW64 : WG_TGT_ROW)
+                                               : WG_TGT_TAP;
+    return (tgt + pl.base() - 1) / pl.base();
+}
+// correction 1, the cap: every workgroup keeps >= WG_MINROWS rows of reduction ...
+static long long wg_split_cap(const WgPlan& pl) {
+    const long long M = pl.p.M, base = pl.base();
+    long long cap = M / WG_MINROWS > 0 ? M / WG_MINROWS : 1;
+    if (pl.p.kt * pl.p.kh * pl.p.kw == 1 && cap * base < 256) {
+        // ... except short 1 x 1 layers (shortcut and attention projections on <= 16-pixel maps): 16 workgroups of 4096 rows each took
+        // 110-150 us for 4 GFLOP -- slices down to 256 rows until every CU has a workgroup (round 5)
+        const long long want = (256 + base - 1) / base, cap2 = M / 256;
+        cap = cap2 < want ? (cap2 > cap ? cap2 : cap) : want;
+    }
+    return cap;
+}
+static void wg_choose_split(const dvd_wgrad_desc* d, WgPlan& pl) {
+    const bool automatic = d->msplit < 1;
+    const long long M = pl.p.M, base = pl.base();
+    long long msplit = d->msplit;
+    if (automatic) {
+        const long long cap = wg_split_cap(pl);
+        msplit = wg_split_target(pl);
+        if (msplit > cap) msplit = cap;
+        // correction 2, whole rounds: the workgroups run `conc` at a time (register / LDS limited); a grid a few workgroups over a
+        // multiple of that pays a full extra round (20 x 103 = 2060 workgroups = 8.05 rounds of 256 -> 9 rounds)
+        const int per_cu = (pl.family != WG_TAP && (pl.bm == 256 || pl.bn == 128)) ? 1 : (pl.family == WG_ROW && pl.bm == 64) ? 3 : 2;
+        const long long conc = WG_CUS * per_cu;
+        if (base * msplit > conc) {
+            const long long rounds = (base * msplit + conc / 2) / conc;           // nearest
+            const long long ms2 = rounds * conc / base;
+            if (ms2 >= 1 && ms2 <= cap) msplit = ms2;
+        }
+    }
+    // correction 3, the 32-bit offset cap: a workgroup's row slice is addressed with 32-bit byte offsets; slices are whole 32-row steps
+    long long rows = (M + msplit - 1) / msplit;
+    const long long ldy_eff = pl.fold ? 4ll * d->ldy : d->ldy;     // (folded: a slice of input pixels spans four times as many rows of dy)
+    const long long rowcap = (1ll << 31) / ((d->ldx > ldy_eff ? d->ldx : ldy_eff) * pl.esz);
+    if (rows > rowcap) rows = rowcap;
+    rows = (rows + 31) / 32 * 32;
+    if (rows < 32) rows = 32;
+    msplit = (M + rows - 1) / rows;
+    // correction 4, fill the last round (one wave per SIMD): the offset cap can undo the whole-round rounding (configs[3]: 3.1 M x
+    // 512 -> 512 behind a 1536-wide dy: 5 slices x 80 workgroups = 1.56 rounds of one workgroup per CU)
+    const long long wg = base * msplit;
+    if (automatic && pl.family == WG_ROW4 && wg > WG_CUS && wg % WG_CUS > 0 && wg % WG_CUS < 192) {
+        const long long ms2 = ((wg + WG_CUS - 1) / WG_CUS * WG_CUS) / base;
+        if (ms2 > msplit && M / ms2 >= 2048) {
+            rows = ((M + ms2 - 1) / ms2 + 31) / 32 * 32;
+            msplit = (M + rows - 1) / rows;
+        }
+    }
+    pl.msplit = msplit;
+    pl.p.rows_per_split = (int)rows;
+    pl.grid = dim3((unsigned)base, 1, (unsigned)msplit);
+}
+
+// The plan of a request.  A 3 x 3 layer over a nearest-x2 upsampled input is planned on the input grid when the folded form applies
+// (see conv_wgrad_row4_kernel<.., FOLD>): whole 64-channel blocks of Cout, 128-wide input-channel tiles, a slice workspace
+// (`may_fold`: the caller supplied one, or is asking for its size) and enough rows for the one-wave-per-SIMD tile.
+static WgPlan wgrad_plan(const dvd_wgrad_desc* d, bool may_fold) {
+    WgPlan pl{};
+    auto plan1 = [&pl](const dvd_wgrad_desc* q, bool fold) {
+        int rc = wg_fill_request(q, pl);
+        if (rc == DVD_OK) rc = wg_choose_tile(q, fold, pl);
+        if (rc == DVD_OK) wg_choose_split(q, pl);
+        return rc;
+    };
+    pl.rc = DVD_E_SHAPE;
+    if (may_fold && d && d->up2 && d->dtype == DVD_BF16 && d->kt == 1 && d->kh == 3 && d->kw == 3 && d->T == 1 &&
         d->Cout % 64 == 0 && d->Cy >= d->Cout && !((d->H | d->W) & 1)) {
         dvd_wgrad_desc e = *d;
         e.H = d->H / 2; e.W = d->W / 2; e.up2 = 0;
         e.Cout = e.Cy = 4 * d->Cout;
-        if (wgrad_plan1(&e, p, grid, ta, tb, msplit, mode, true) == DVD_OK) {
+        pl.rc = plan1(&e, true);
+        if (pl.rc == DVD_OK) {
             const size_t M4 = (size_t)d->frames * d->T * d->H * d->W;
-            p.dy_bytes = ((M4 - 1) * (size_t)d->ldy + d->Cy) * 2;
-            p.fold = 1; p.cout_f = d->Cout;
-            return DVD_OK;
+            pl.p.dy_bytes = ((M4 - 1) * (size_t)d->ldy + d->Cy) * 2;
+            pl.p.fold = 1; pl.p.cout_f = d->Cout;
         }
     }
-    return wgrad_plan1(d, p, grid, ta, tb, msplit, mode, false);
+    if (pl.rc != DVD_OK) pl.rc = plan1(d, false);
+    if (pl.rc != DVD_OK) return pl;
+    // the slice workspace: partial tiles of every (slice, workgroup, tap of its tile), then the bias partials of every (slice,
+    // workgroup) -- one-tap kernel: (slice, out-channel tile)
+    pl.kw_tile = pl.family == WG_TAP ? 1 : d->kw;
+    pl.tile_floats = (long long)ws_tile_off(pl.msplit, pl.grid.x, 0, pl.kw_tile, 0, pl.bm * pl.bn);
+    pl.bias_floats = (long long)ws_bias_off(pl.msplit, pl.family == WG_TAP ? (unsigned)pl.p.tiles_co : pl.grid.x, 0, pl.bm);
+    return pl;
 }
 
 extern "C" long long dvd_conv_wgrad_ws_floats(const dvd_wgrad_desc* d) {
-    WgK p; dim3 grid; int ta, tb, mode; long long msplit;
     if (const long long thin = dvd_wgrad_thin_ws_floats(d)) return thin;       // 3 (8) channels on one side: wgrad_thin.hip
-    if (wgrad_plan(d, p, grid, ta, tb, msplit, mode, true) != DVD_OK || (msplit <= 1 && !p.fold)) return 0;
-    if (mode >= 1) return msplit * (long long)grid.x * d->kw * (ta * 64) * (tb * 64) + msplit * (long long)grid.x * (ta * 64);   // + bias partials
-    return msplit * (long long)grid.x * (ta * 64) * (tb * 64) + msplit * (long long)p.tiles_co * (ta * 64);      // + bias partials
+    const WgPlan pl = wgrad_plan(d, true);
+    if (pl.rc != DVD_OK || (pl.msplit <= 1 && !pl.fold)) return 0;             // a single slice adds straight into dw
+    return pl.total();
 }
 
+// ============================================================================ dispatch
+// One launcher per filter-row family (it branches on relu_in; the one-tap kernel takes relu_in at run time), selected by a flat
+// switch over the plan.
+namespace {
+
+template <int WM, int KW, bool UP2 = false, int NH = 2>
+void launch_row(const WgPlan& pl, hipStream_t st) {
+    if (pl.p.relu_in) conv_wgrad_row_kernel<WM, KW, true, UP2, NH><<<pl.grid, WM * NH * 64, 0, st>>>(pl.p);
+    else conv_wgrad_row_kernel<WM, KW, false, UP2, NH><<<pl.grid, WM * NH * 64, 0, st>>>(pl.p);
+}
+template <int KW, int AW, int BW, int WCO, int WCI, int DEPTH, bool FOLD = false>
+void launch_row4(const WgPlan& pl, hipStream_t st) {
+    if (pl.p.relu_in) conv_wgrad_row4_kernel<KW, AW, BW, WCO, WCI, true, DEPTH, FOLD><<<pl.grid, 256, 0, st>>>(pl.p);
+    else conv_wgrad_row4_kernel<KW, AW, BW, WCO, WCI, false, DEPTH, FOLD><<<pl.grid, 256, 0, st>>>(pl.p);
+}
+
+// switch key of a kernel.  kw / up2 select nothing in the one-tap family (0 there); f32 selects only there.
+constexpr unsigned wg_key(WgFamily family, int bm, int bn, int kw, int up2, int depth, int fold, int f32 = 0) {
+    return (unsigned)family | (bm / 64) << 2 | (bn / 64) << 5 | kw << 8 | up2 << 11 | depth << 12 | fold << 14 | f32 << 15;
+}
+
+// false: no kernel for this plan (a planner bug: nothing falls back)
+bool wg_launch(const WgPlan& pl, hipStream_t st) {
+    const bool tap = pl.family == WG_TAP;
+    switch (wg_key(pl.family, pl.bm, pl.bn, tap ? 0 : pl.p.kw, tap ? 0 : pl.p.up2 != 0, pl.depth, pl.fold, tap && pl.esz == 4)) {
+    //            family   bm   bn   kw up2 depth fold
+    case wg_key(WG_TAP,  256, 128, 0, 0, 0, 0):    conv_wgrad_kernel<bf16_t, 4, 2><<<pl.grid, NT, 0, st>>>(pl.p); break;
+    case wg_key(WG_TAP,  128, 256, 0, 0, 0, 0):    conv_wgrad_kernel<bf16_t, 2, 4><<<pl.grid, NT, 0, st>>>(pl.p); break;
+    case wg_key(WG_TAP,  128, 128, 0, 0, 0, 0):    conv_wgrad_kernel<bf16_t, 2, 2><<<pl.grid, NT, 0, st>>>(pl.p); break;
+    case wg_key(WG_TAP,  128, 128, 0, 0, 0, 0, 1): conv_wgrad_kernel<float, 2, 2><<<pl.grid, NT, 0, st>>>(pl.p); break;
+    case wg_key(WG_ROW,   64,  64, 3, 0, 0, 0):    launch_row<1, 3>(pl, st); break;
+    case wg_key(WG_ROW,   64,  64, 5, 0, 0, 0):    launch_row<1, 5>(pl, st); break;
+    case wg_key(WG_ROW,  128,  64, 3, 0, 0, 0):    launch_row<2, 3>(pl, st); break;
+    case wg_key(WG_ROW,  128,  64, 5, 0, 0, 0):    launch_row<2, 5>(pl, st); break;
+    case wg_key(WG_ROW,  256,  64, 3, 0, 0, 0):    launch_row<4, 3>(pl, st); break;
+    case wg_key(WG_ROW,  256,  64, 5, 0, 0, 0):    launch_row<4, 5>(pl, st); break;
+    case wg_key(WG_ROW,   64,  64, 3, 1, 0, 0):    launch_row<1, 3, true>(pl, st); break;
+    case wg_key(WG_ROW,  128,  64, 3, 1, 0, 0):    launch_row<2, 3, true>(pl, st); break;
+    case wg_key(WG_ROW,  256,  64, 3, 1, 0, 0):    launch_row<4, 3, true>(pl, st); break;
+    case wg_key(WG_ROW,  128, 128, 3, 0, 0, 0):    launch_row<2, 3, false, 4>(pl, st); break;     // (wg_choose_tile takes this tile for 5 taps only)
+    case wg_key(WG_ROW,  128, 128, 5, 0, 0, 0):    launch_row<2, 5, false, 4>(pl, st); break;
+    case wg_key(WG_ROW4, 256, 128, 3, 0, 1, 0):    launch_row4<3, 4, 2, 2, 2, 1>(pl, st); break;
+    case wg_key(WG_ROW4, 256, 128, 3, 0, 2, 0):    launch_row4<3, 4, 2, 2, 2, 2>(pl, st); break;
+    case wg_key(WG_ROW4, 128, 128, 3, 0, 2, 0):    launch_row4<3, 4, 1, 1, 4, 2>(pl, st); break;
+    case wg_key(WG_ROW4, 128, 128, 3, 0, 2, 1):    launch_row4<3, 4, 1, 1, 4, 2, true>(pl, st); break;
+    case wg_key(WG_ROW4, 256,  64, 5, 0, 2, 0):    launch_row4<5, 4, 1, 2, 2, 2>(pl, st); break;
+    case wg_key(WG_ROW4, 128, 128, 5, 0, 2, 0):    launch_row4<5, 4, 1, 1, 4, 2>(pl, st); break;
+    default: return false;
+    }
+    return true;
+}
+
+}  // namespace
+
 extern "C" int dvd_conv_wgrad(const dvd_wgrad_desc* d, void* stream) {
-    WgK p; dim3 grid; int ta, tb, mode; long long msplit;
-    const int rc = wgrad_plan(d, p, grid, ta, tb, msplit, mode, d && d->ws != nullptr);
-    if (rc != DVD_OK) return rc;
-    const int ntaps = d->kt * d->kh * d->kw;
+    WgPlan pl = wgrad_plan(d, d && d->ws != nullptr);
+    if (pl.rc != DVD_OK) return pl.rc;
+    WgK& p = pl.p;
+    hipStream_t st = (hipStream_t)stream;
+    const int ntaps = d->kt * d->kh * d->kw, nslice = (int)pl.msplit, gx = (int)pl.grid.x;
     const long long Mreal = (long long)d->frames * d->T * d->H * d->W;
     if (d->ws && dvd_wgrad_thin_ws_floats(d)) {    // the thin ends of the networks (stems, RGB layer): taps folded into the matrix dimension
         if (d->overwrite && (d->s_tap != 1 || d->s_ci != ntaps || d->s_co != (long long)d->Cin_real * ntaps)) return DVD_E_ARG;
@@ -1487,80 +1524,41 @@ extern "C" int dvd_conv_wgrad(const dvd_wgrad_desc* d, void* stream) {
         prof.r.variant = 3;
         return dvd_wgrad_thin(d, stream);
     }
-    if (d->ws && (msplit > 1 || p.fold)) p.ws = d->ws;         // two-phase reduction; a single slice adds straight into dw (not the folded form)
+    if (d->ws && (pl.msplit > 1 || pl.fold)) {     // two-phase reduction; a single slice adds straight into dw (not the folded form)
+        p.ws = d->ws;
+        p.wsb = d->ws + pl.tile_floats;
+    }
     const int overwrite = d->overwrite != 0;       // dw = result instead of dw += result (the caller need not zero it)
     if (overwrite) {
         if (d->s_tap != 1 || d->s_ci != ntaps || d->s_co != (long long)d->Cin_real * ntaps) return DVD_E_ARG;   // dense [co][ci][tap] only
-        if (!p.ws && hipMemsetAsync(d->dw, 0, (size_t)d->Cout * d->Cin_real * ntaps * sizeof(float), (hipStream_t)stream) != hipSuccess)
+        if (!p.ws && hipMemsetAsync(d->dw, 0, (size_t)d->Cout * d->Cin_real * ntaps * sizeof(float), st) != hipSuccess)
             return DVD_E_LAUNCH;                   // single slice: the kernel adds with atomics
     }
-    p.wsb = !p.ws ? nullptr : mode >= 1 ? p.ws + msplit * (long long)grid.x * d->kw * (ta * 64) * (tb * 64)
-                                        : p.ws + msplit * (long long)grid.x * (ta * 64) * (tb * 64);
-    ProfScope prof(1, 2.0 * (double)Mreal * d->Cout * d->Cin_real * ntaps, stream, (int)Mreal, d->C, d->Cout, ntaps, (int)msplit,
+    ProfScope prof(1, 2.0 * (double)Mreal * d->Cout * d->Cin_real * ntaps, stream, (int)Mreal, d->C, d->Cout, ntaps, nslice,
                    d->up2 | (d->relu_in << 1));
-    hipStream_t st = (hipStream_t)stream;
-    prof.r.variant = mode == 2 ? 4 : mode == 1 ? 1 : 2;        // (dvd_prof_report_variants: 1 = 8-wave filter-row tiles, 2 = one tap, 3 = thin ends, 4 = one wave per SIMD)
-    if (mode >= 1) {
-#define LAUNCH_ROW(WM_, KW_)                                                                        \
-        do { if (d->relu_in) conv_wgrad_row_kernel<WM_, KW_, true><<<grid, WM_ * 128, 0, st>>>(p);      \
-             else conv_wgrad_row_kernel<WM_, KW_, false><<<grid, WM_ * 128, 0, st>>>(p); } while (0)
-#define LAUNCH_ROW_UP(WM_)                                                                          \
-        do { if (d->relu_in) conv_wgrad_row_kernel<WM_, 3, true, true><<<grid, WM_ * 128, 0, st>>>(p);  \
-             else conv_wgrad_row_kernel<WM_, 3, false, true><<<grid, WM_ * 128, 0, st>>>(p); } while (0)
-#define LAUNCH_ROW_W(KW_)                                                                           \
-        do { if (d->relu_in) conv_wgrad_row_kernel<2, KW_, true, false, 4><<<grid, 512, 0, st>>>(p);    \
-             else conv_wgrad_row_kernel<2, KW_, false, false, 4><<<grid, 512, 0, st>>>(p); } while (0)
-        if (mode == 2) {
-#define LAUNCH_ROW4(KW_, AW_, BW_, WCO_, WCI_, DEPTH_)                                                                        \
-            do { if (d->relu_in) conv_wgrad_row4_kernel<KW_, AW_, BW_, WCO_, WCI_, true, DEPTH_><<<grid, 256, 0, st>>>(p);       \
-                 else conv_wgrad_row4_kernel<KW_, AW_, BW_, WCO_, WCI_, false, DEPTH_><<<grid, 256, 0, st>>>(p); } while (0)
-            if (p.fold) {
-                if (d->relu_in) conv_wgrad_row4_kernel<3, 4, 1, 1, 4, true, 2, true><<<grid, 256, 0, st>>>(p);
-                else conv_wgrad_row4_kernel<3, 4, 1, 1, 4, false, 2, true><<<grid, 256, 0, st>>>(p);
-                WgFoldRedK r{p.ws, p.dw, (int)msplit, (int)grid.x, p.tiles_ci, d->Cout, p.Cin_real, p.s_co, p.s_ci, p.s_tap, overwrite};
-                wgrad_fold_reduce_kernel<<<cdiv(9ll * d->Cout * ((p.Cin_real + 3) / 4), 256), 256, 0, st>>>(r);
-                if (p.dbias) {
-                    WgFoldBiasK b{p.wsb, p.dbias, (int)msplit, (int)grid.x, p.tiles_ci, d->Cout};
-                    wgrad_fold_bias_reduce_kernel<<<cdiv(d->Cout, 32), 1024, 0, st>>>(b);
-                }
-                return launch_status();
-            }
-            if (d->kw == 3) { if (ta == 4 && p.dbias) LAUNCH_ROW4(3, 4, 2, 2, 2, 1); else if (ta == 4) LAUNCH_ROW4(3, 4, 2, 2, 2, 2); else LAUNCH_ROW4(3, 4, 1, 1, 4, DVD_ROW4_DEPTH); }
-            else            { if (ta == 4) LAUNCH_ROW4(5, 4, 1, 2, 2, 2); else LAUNCH_ROW4(5, 4, 1, 1, 4, 2); }
-#undef LAUNCH_ROW4
-        } else
-        if (d->up2) { if (ta == 4) LAUNCH_ROW_UP(4); else if (ta == 2) LAUNCH_ROW_UP(2); else LAUNCH_ROW_UP(1); }
-        else if (tb == 2) { if (d->kw == 5) LAUNCH_ROW_W(5); else LAUNCH_ROW_W(3); }
-        else
-        if (ta == 4)      { if (d->kw == 5) LAUNCH_ROW(4, 5); else LAUNCH_ROW(4, 3); }
-        else if (ta == 2) { if (d->kw == 5) LAUNCH_ROW(2, 5); else LAUNCH_ROW(2, 3); }
-        else              { if (d->kw == 5) LAUNCH_ROW(1, 5); else LAUNCH_ROW(1, 3); }
-#undef LAUNCH_ROW
-#undef LAUNCH_ROW_UP
-#undef LAUNCH_ROW_W
-        if (p.ws) {
-            WgRowRedK r{p.ws, p.dw, (int)msplit, (int)grid.x, p.tiles_co, p.tiles_ci, ta * 64, tb * 64, d->kw, p.Cout, p.Cin_real,
-                        p.s_co, p.s_ci, p.s_tap, overwrite};
-            const long long n = (long long)grid.x * r.KW * r.BMc * r.BNc;
-            wgrad_row_reduce_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(r);
-            if (p.dbias) {
-                WgBiasRedK b{p.wsb, p.dbias, (int)msplit, (int)grid.x, p.tiles_co, p.tiles_ci, d->kw, d->kt, ta * 64, p.Cout};
-                wgrad_row_bias_reduce_kernel<<<p.tiles_co * (ta * 64 / 32), 1024, 0, st>>>(b);
-            }
+    // (dvd_prof_report_variants: 1 = 8-wave filter-row tiles, 2 = one tap, 3 = thin ends, 4 = one wave per SIMD)
+    prof.r.variant = pl.family == WG_ROW4 ? 4 : pl.family == WG_ROW ? 1 : 2;
+    if (!wg_launch(pl, st)) return DVD_E_SHAPE;
+    if (!p.ws) return launch_status();
+    // second phase: partial tiles -> dw, bias partials -> dbias
+    if (pl.fold) {
+        WgFoldRedK r{p.ws, p.dw, nslice, gx, p.tiles_ci, d->Cout, p.Cin_real, p.s_co, p.s_ci, p.s_tap, overwrite};
+        wgrad_fold_reduce_kernel<<<cdiv(9ll * d->Cout * ((p.Cin_real + 3) / 4), 256), 256, 0, st>>>(r);
+        if (p.dbias) {
+            WgFoldBiasK b{p.wsb, p.dbias, nslice, gx, p.tiles_ci, d->Cout};
+            wgrad_fold_bias_reduce_kernel<<<cdiv(d->Cout, 32), 1024, 0, st>>>(b);
         }
         return launch_status();
     }
-    if (d->dtype == DVD_BF16) {
-        if (ta == 4) conv_wgrad_kernel<bf16_t, 4, 2><<<grid, NT, 0, st>>>(p);
-        else if (tb == 4) conv_wgrad_kernel<bf16_t, 2, 4><<<grid, NT, 0, st>>>(p);
-        else conv_wgrad_kernel<bf16_t, 2, 2><<<grid, NT, 0, st>>>(p);
-    } else conv_wgrad_kernel<float, 2, 2><<<grid, NT, 0, st>>>(p);
-    if (p.ws) {
-        WgRedK r{p.ws, p.dw, (int)msplit, (int)grid.x, p.tiles_co * p.tiles_ci, p.tiles_ci, ta * 64, tb * 64, p.Cout,
-                 p.Cin_real, p.s_co, p.s_ci, p.s_tap, overwrite};
-        const long long n = (long long)grid.x * r.BMc * r.BNc;
-        wgrad_reduce_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(r);
-        if (p.dbias) wgrad_bias_reduce_kernel<<<cdiv(p.Cout, 64), 1024, 0, st>>>(p.wsb, p.dbias, (int)msplit, p.tiles_co, ta * 64, p.Cout);
+    WgRowRedK r{p.ws, p.dw, nslice, gx, p.tiles_co, p.tiles_ci, pl.bm, pl.bn, pl.kw_tile, p.Cout, p.Cin_real, p.s_co, p.s_ci, p.s_tap, overwrite};
+    const long long n = pl.tile_floats / nslice;                     // partial-tile elements of one slice
+    wgrad_row_reduce_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(r);
+    if (p.dbias) {
+        if (pl.family == WG_TAP) wgrad_bias_reduce_kernel<<<cdiv(p.Cout, 64), 1024, 0, st>>>(p.wsb, p.dbias, nslice, p.tiles_co, pl.bm, p.Cout);
+        else {
+            WgBiasRedK b{p.wsb, p.dbias, nslice, gx, p.tiles_co, p.tiles_ci, d->kw, d->kt, pl.bm, p.Cout};
+            wgrad_row_bias_reduce_kernel<<<p.tiles_co * (pl.bm / 32), 1024, 0, st>>>(b);
+        }
     }
     return launch_status();
 }

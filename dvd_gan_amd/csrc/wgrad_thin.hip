@@ -192,7 +192,7 @@ ThinPlan thin_plan(const dvd_wgrad_desc* d) {
 
 }  // namespace
 
-// (internal, called by dvd_conv_wgrad / dvd_conv_wgrad_ws_floats of conv_igemm.hip)  floats of workspace, 0 = not served here
+// (internal, called by dvd_conv_wgrad / dvd_conv_wgrad_ws_floats of conv_wgrad.hip)  floats of workspace, 0 = not served here
 long long dvd_wgrad_thin_ws_floats(const dvd_wgrad_desc* d) {
     const ThinPlan q = thin_plan(d);
     return q.ok ? (long long)(q.G + PARTS) * q.per : 0;

@@ -136,6 +136,36 @@ def test_dispatch_queries_need_no_gpu():
     assert ws(L.BF16, 64, 32, 32, 128, 3) == 65536 * 256      # unsplit: one slab of whole 256-column tiles
 
 
+@pytest.mark.parametrize("frames,S,cin,cout,k,up2,floats", [
+    (3072, 16, 256, 256, 3, 0, 24837120),
+    (3072, 32, 128, 128, 3, 0, 12566400),
+    (3072, 32, 128, 256, 5, 0, 20544000),
+    (3072, 32, 256, 128, 5, 0, 20512000),
+    (3072, 32, 256, 384, 5, 0, 19691520),
+    (3072, 64, 64, 64, 3, 0, 9486336),
+    (3008, 4, 256, 256, 3, 0, 6521856),
+    (3072, 4, 256, 256, 3, 0, 7114752),
+    (3072, 64, 128, 64, 3, 1, 12615680),
+    (64, 32, 128, 256, 3, 0, 4743168),
+    (64, 8, 256, 512, 3, 0, 0),
+])
+def test_wgrad_workspace_sizes_are_pinned(frames, S, cin, cout, k, up2, floats):
+    """dvd_conv_wgrad_ws_floats on benchmark shapes: the planner's tile, slice count and the slice-workspace layout (partial tiles +
+    bias partials) together decide this number, so a change of any of them shows here without a GPU.  Values computed on the CPU from
+    the code before the planner was split into steps.  (Equal totals do not prove equal plans: 256 x 64 and 128 x 128 tiles give the
+    same size.)"""
+    from dvd_gan_amd import lib as L
+    lib = L.lib()
+    pad8 = lambda c: (c + 7) // 8 * 8
+    w = L.WgradDesc()
+    w.dtype, w.frames, w.T, w.H, w.W = L.BF16, frames, 1, S, S
+    w.C, w.ldx, w.Cin_real, w.Cout, w.Cy, w.ldy = pad8(cin), pad8(cin), cin, cout, pad8(cout), pad8(cout)
+    w.kt, w.kh, w.kw, w.up2, w.msplit = 1, k, k, up2, 0
+    w.s_co, w.s_ci, w.s_tap = cin * k * k, k * k, 1
+    w.x = w.dy = w.dw = 1                            # never dereferenced by the query
+    assert lib.dvd_conv_wgrad_ws_floats(ctypes.byref(w)) == floats
+
+
 @pytest.mark.parametrize("hw", [32, 64])
 @pytest.mark.parametrize("cin,cout,kind", [(8, 64, 2), (64, 8, 3)])
 def test_pool2_requests_skip_the_thin_kernels(cin, cout, kind, hw):

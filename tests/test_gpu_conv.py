@@ -197,6 +197,14 @@ def test_conv_forward_dgrad_wgrad(case, dtype):
         dw4 = torch.zeros_like(dw)
         K.conv_wgrad(xc, gyc, dw4, ks, Cout, Cin, up2=up2, relu_in=relu_in, msplit=2)
         assert rel(dw4.cpu(), wq_.grad) < 1e-5
+        # overwrite mode (what the spectrally normalised layers use): the same bits as accumulating into zeros, whatever dw held --
+        # through the reduce kernels' store tail (two slices) and through memset + one atomic addition per element (one slice)
+        dw5 = torch.full_like(dw, 7.0)
+        K.conv_wgrad(xc, gyc, dw5, ks, Cout, Cin, up2=up2, relu_in=relu_in, msplit=2, overwrite=True)
+        assert torch.equal(dw5, dw4)
+        dw6 = torch.full_like(dw, 7.0)
+        K.conv_wgrad(xc, gyc, dw6, ks, Cout, Cin, up2=up2, relu_in=relu_in, msplit=1, overwrite=True)
+        assert torch.equal(dw6, dw2)
 
 
 @pytest.mark.parametrize("case", [(5, (64, 64), (3, 3), True, 1, False), (3, (6, 32, 32), (3, 3, 3), False, 0, False),
