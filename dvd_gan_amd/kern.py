@@ -557,3 +557,18 @@ def swap_(a, b):
     """Exchange the contents of two fp32 tensors of equal size."""
     assert a.numel() == b.numel() and a.dtype == b.dtype == torch.float32
     L.check(L.lib().dvd_swap_f32(L.ptr(a), L.ptr(b), _ll(a.numel()), L.stream()))
+
+
+METRICS_SIGNED, METRICS_QUANTIZE = 1, 2          # DVD_METRICS_* of include/dvdgan_hip.h
+
+
+def frame_metrics(pred, p_strides, target, t_strides, B, T, Cc, H, W, flags, mse, ssim):
+    """dvd_frame_metrics on two device fp32 tensors (views welcome: only their data pointers are taken) whose (batch, time,
+    channel) strides in elements are p_strides / t_strides and whose H x W planes are contiguous; fills the fp32 device
+    buffers mse / ssim (B * T values each, frame b * T + t)."""
+    lib = L.lib()
+    nbytes = lib.dvd_frame_metrics_ws_bytes(_ll(B), T, Cc, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device) if nbytes else None
+    L.check(lib.dvd_frame_metrics(C.c_void_p(pred.data_ptr()), *(_ll(s) for s in p_strides),
+                                  C.c_void_p(target.data_ptr()), *(_ll(s) for s in t_strides),
+                                  _ll(B), T, Cc, H, W, int(flags), L.ptr(mse), L.ptr(ssim), L.ptr(ws), L.stream()))

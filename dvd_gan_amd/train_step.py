@@ -13,7 +13,8 @@ Differences that do not change results: the dead D weight-gradients of the gener
 computed; Adam is one fused launch per network; gradients are exchanged with RCCL (dist.py).
 Beyond the reference: config.ema_decay > 0 keeps an exponential moving average of the generator's weights, updated inside the
 generator's Adam launch (optim.FlatAdam); `ema_weights()` / `sample(use_ema=True)` / `predict(use_ema=True)` compute with it and
-`save_models` writes it as `{step}_G_ema.pth`.
+`save_models` writes it as `{step}_G_ema.pth`.  A frame-conditional Trainer also has `rollout()` (autoregressive prediction past
+n_frames) and `evaluate_prediction()` (PSNR / SSIM curves over the horizon, mean and best of N sampled futures; metrics.py).
 Out of scope: tensorboard logging, sample grids, dataset loaders.
 """
 import contextlib
@@ -553,6 +554,115 @@ class Trainer(object):
             finally:
                 self.G.train()
         return denorm(fake)
+
+    # ---- autoregressive rollouts and the prediction metrics (no counterpart in the reference)
+    def _rollout_raw(self, cond, labels, horizon, draw_z):
+        """The chunks of a rollout, RAW ([-1, 1], as the generator wrote them): [B, horizon, 3, H, W].  cond / labels on the
+        device; draw_z() -> the z of the next chunk (a device tensor is used as it is, a host tensor goes up without stalling the
+        host); G in eval mode and the weights chosen by the caller."""
+        K_, T = self.n_cond, self.n_frames
+        chunks, ctx = [], cond
+        for done in range(0, horizon, T):
+            fake = self.G(to_device_async(draw_z(), self.device), labels, cond=ctx)
+            chunks.append(fake)
+            if done + T < horizon:
+                # the last K frames of [context | everything generated so far], untouched: no denorm and back
+                ctx = (fake[:, -K_:] if T >= K_ else torch.cat([ctx, fake], 1)[:, -K_:]).contiguous()
+        out = chunks[0] if len(chunks) == 1 else torch.cat(chunks, 1)
+        return out if out.shape[1] == horizon else out[:, :horizon].contiguous()
+
+    def _rollout_args(self, what, cond, horizon, n_frames_ctx):
+        if not self.n_cond:
+            raise RuntimeError(f"{what}() needs a frame-conditional Trainer (config.n_cond > 0); use sample()")
+        if int(horizon) < 1:
+            raise ValueError(f"horizon={horizon}")
+        if cond.dim() != 5 or cond.shape[n_frames_ctx[0]] != n_frames_ctx[1]:
+            raise ValueError(f"{what}(): unexpected clip shape {tuple(cond.shape)} for n_cond={self.n_cond}, horizon={horizon}")
+
+    @torch.no_grad()
+    def rollout(self, cond, labels, horizon, z=None, *, use_ema=False, standing_stats=None, truncation=None):
+        """Autoregressive prediction past the training length: cond [B, K, 3, H, W] context frames in [-1, 1], labels [B] ->
+        [B, horizon, 3, H, W] in [0, 1].  n_frames are predicted at a time; every further chunk is conditioned on the last K
+        frames of [context | everything generated so far] exactly as the generator produced them (raw [-1, 1] values), and the
+        last chunk is cut to `horizon` -- so horizon == n_frames is predict() bit for bit.  z [B, z_dim] serves every chunk when
+        given; otherwise each chunk draws its own (truncated to [-truncation, truncation] when that is given).  use_ema /
+        standing_stats as in predict(): the ema_weights() block is entered ONCE around the whole rollout, the standing-statistics
+        passes run once, on the caller's cond / labels.
+        Unlike predict(), which advances the generator's spectral-norm u / v even in eval mode (quirk 2), a rollout leaves NO trace:
+        u / v advance from chunk to chunk inside it and are put back at the end, so weights, u / v, batch-norm statistics and
+        counters are bit-equal before and after and a rollout in the middle of training does not move the run."""
+        self._rollout_args("rollout", cond, horizon, (1, self.n_cond))
+        B = cond.shape[0]
+        if z is not None and truncation is not None:
+            raise ValueError("truncation applies to z drawn here: pass z=None, or truncate the z you pass")
+        if z is not None:
+            z = to_device_async(z, self.device)                 # one upload serves every chunk
+        draw = (lambda: z) if z is not None else (lambda: self._draw_z(B, truncation))
+        with self._sampling_weights(use_ema, standing_stats, cond, labels):
+            frozen = self._g_frozen_tensors()
+            saved = [t.clone() for t in frozen]
+            self.G.eval()
+            try:
+                raw = self._rollout_raw(cond.to(self.device, torch.float32),
+                                        to_device_async(self._check_labels(labels), self.device), int(horizon), draw)
+            finally:
+                self.G.train()
+                for t, old in zip(frozen, saved):
+                    t.copy_(old)
+        return denorm(raw)
+
+    @torch.no_grad()
+    def evaluate_prediction(self, clips, labels, *, horizon=None, n_samples=1, seed=0, use_ema=False, standing_stats=None,
+                            truncation=None, quantize=True):
+        """PSNR / SSIM of predicted futures against the held-out frames of real clips.  clips [B, 3, K + horizon, H, W] in
+        [-1, 1] as the loader delivers them (horizon defaults to n_frames; longer ones are rolled out like rollout()), labels [B].
+        Per clip n_samples futures are drawn, sample s with one z for all its chunks, z from a PRIVATE generator seeded with
+        `seed` (neither the default generator nor noise_gen is touched; truncation as in predict()): all n_samples z are drawn
+        first, in sample order, and go to the device in one upload before the loop.  Each future goes through
+        metrics.frame_metrics(signed=True, quantize=quantize) against the view clips[:, :, K:] -- no denorm pass, no permuted copy
+        -- into one device table that is copied to the host once; nothing inside the loop makes the host wait for the device.
+        Every future starts from the same generator state: the spectral-norm u / v, which advance with every generator pass even
+        in eval mode, are put back after each sample, so sample s is exactly rollout(cond, labels, horizon, z=z_s) and the
+        training state (weights, u / v, batch-norm statistics and counters) is bit-equal before and after the call.  -> dict of fp64 numpy arrays:
+        psnr, ssim [horizon]: mean over clips and samples; psnr_best, ssim_best [horizon]: mean over clips of the sample with the
+        highest horizon-mean of THAT metric (best-of-N, chosen per metric); table: {"mse", "ssim"} [B, n_samples, horizon].
+        A frame predicted exactly (mse = 0) has PSNR +inf and makes every mean it enters +inf.
+        use_ema / standing_stats as in predict(): the ema_weights() block is entered once around all samples."""
+        from . import metrics as M
+        K_ = self.n_cond
+        horizon = self.n_frames if horizon is None else int(horizon)
+        self._rollout_args("evaluate_prediction", clips, horizon, (2, K_ + horizon))
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError(f"n_samples={n_samples}")
+        B = clips.shape[0]
+        gen = torch.Generator().manual_seed(int(seed))
+        clips = to_device_async(clips, self.device).to(torch.float32)
+        frames = clips.permute(0, 2, 1, 3, 4)                          # [B, K + horizon, 3, H, W], a view
+        cond, target = frames[:, :K_].contiguous(), frames[:, K_:]
+        labels_d = to_device_async(self._check_labels(labels), self.device)
+        zs = torch.stack([torch.randn(B, self.z_dim, generator=gen) if truncation is None
+                          else truncated_z(B, self.z_dim, truncation, generator=gen) for _ in range(n_samples)])
+        zs = to_device_async(zs, self.device)                  # [n_samples, B, z_dim]: one upload, before the loop
+        mse = torch.empty(n_samples, B, horizon, dtype=torch.float32, device=self.device)
+        ssim = torch.empty_like(mse)
+        with self._sampling_weights(use_ema, standing_stats, cond, labels):
+            frozen = self._g_frozen_tensors()
+            saved = [t.clone() for t in frozen]
+            self.G.eval()
+            try:
+                for s in range(n_samples):
+                    z = zs[s]
+                    raw = self._rollout_raw(cond, labels_d, horizon, lambda: z)
+                    M.frame_metrics(raw, target, signed=True, quantize=quantize, out=(mse[s], ssim[s]))
+                    for t, old in zip(frozen, saved):
+                        t.copy_(old)
+            finally:
+                self.G.train()
+                for t, old in zip(frozen, saved):
+                    t.copy_(old)
+        table = torch.stack([mse, ssim]).permute(0, 2, 1, 3).cpu().numpy()          # the one copy to the host
+        return M.aggregate_prediction(table[0], table[1])
 
     # ---- trainer.py:337-343 / 375-382: reference-compatible checkpoints
     def save_models(self, step):

@@ -417,6 +417,27 @@ int dvd_ema_step(float* ema, const float* p, long long n, float decay, void* str
  * no-op; buffers that overlap in part are not supported (not checked: both would be corrupted). */
 int dvd_swap_f32(float* a, float* b, long long n, void* stream);
 
+/* Prediction metrics (metrics.frame_metrics, Trainer.evaluate_prediction; additions: the ABI version stays 13): per-frame MSE and
+ * SSIM of F = B * T predicted frames against target frames, C channels of H x W fp32 each, 11 <= H, W <= 256.  Each operand is a
+ * base pointer with batch, time and channel strides in ELEMENTS; the H x W planes are contiguous (row stride W).  So `pred` can be
+ * the generator's [B][T][C][H][W] and `target` the view [:, :, K:] of a loader clip [B][C][K+T][H][W], without a permuted copy.
+ * mse[b * T + t] = mean over C * H * W of (p - t)^2.  ssim[b * T + t] = the mean SSIM index of Wang et al. 2004 over all
+ * (H - 10) * (W - 10) "valid" windows and the C channels: 11 x 11 Gaussian window, sigma = 1.5, weights normalised to sum 1,
+ * C1 = 0.01^2, C2 = 0.03^2 (L = 1), sigma_x^2 = E[x^2] - mu_x^2.
+ * flags: DVD_METRICS_SIGNED = the operands are in [-1, 1]: x <- clamp((x + 1) / 2, 0, 1) on load; DVD_METRICS_QUANTIZE = after
+ * that, x <- rint(255 x) / 255.  Unknown bits, sides outside [11, 256], C / T / B < 1: DVD_E_SHAPE, before any launch.
+ * Deterministic: a frame's result depends on nothing but that frame's pixels (no atomics; fixed-order sums).  Any base alignment
+ * (16-byte aligned planes with W % 4 == 0 take the vector loads).  `ws`: dvd_frame_metrics_ws_bytes bytes (currently 0: may be
+ * null). */
+#define DVD_METRICS_SIGNED 1
+#define DVD_METRICS_QUANTIZE 2
+#define DVD_METRICS_MIN_SIDE 11
+#define DVD_METRICS_MAX_SIDE 256
+long long dvd_frame_metrics_ws_bytes(long long B, int T, int C, int H, int W);
+int dvd_frame_metrics(const float* pred, long long p_sb, long long p_st, long long p_sc, const float* target,
+                      long long t_sb, long long t_st, long long t_sc, long long B, int T, int C, int H, int W, int flags,
+                      float* mse, float* ssim, void* ws, void* stream);
+
 /* 2-D self attention (Discriminators.py:100-119: bmm, softmax, bmm, gamma*out + x) */
 int dvd_attention_forward(int dtype, const void* qkv, int ldq, int dq, int koff, int voff, const void* x, int ldx, int C,
                           const float* gamma, void* y, void* att_out, float* A, long long frames, int N, void* stream);
