@@ -1,5 +1,5 @@
-// Shared device code of the convolution kernels (conv_igemm.hip, conv_gb.hip, conv_wgrad.hip): the kernel parameter block,
-// LDS tile addressing, and the batched epilogue (direct / split-K slabs / fused ConvGRU gate math / in-launch split-K combine).
+// Shared code of the convolution kernels (conv_igemm.hip, conv_gb.hip, conv_wgrad.hip): the kernel parameter block, the kernel
+// families and group kinds of the forward planner, LDS tile addressing, and the batched epilogue (direct / split-K slabs / fused ConvGRU gate math / in-launch split-K combine).
 #pragma once
 #include "common.h"
 
@@ -550,9 +550,33 @@ struct ConvGroup {
 };
 static_assert(sizeof(ConvGroup) <= 3584, "ConvGroup must fit the kernel argument segment");
 
-// conv_gb.hip (weights from L2, fragment-major): launchers for conv_igemm.hip's dispatch
-void launch_gb(const ConvK& p, int variant, bool relu_in, bool up2, dim3 grid, hipStream_t st);
-void launch_gbs(const ConvK& p, int S, bool big, bool relu_in, dim3 grid, hipStream_t st);
+// The five kernels of a grouped launch (`kind` of dvd_conv_forward_group), read by the entry point's checks, by launch_group
+// and by gru.hip's split-K search: M-tile rows (a member has cdiv(M, rows) of them), whole frames per tile (0: 16-pixel-wide patches
+// of larger frames), frame side (patches: the smallest), accumulator floats of a 128-column tile, workgroups an XCD runs at a time, and the
+// family a member's own plan must name.  The kernel of each kind: kGroupKernel in conv_gb.hip, one entry per row of this table.
+enum ConvFamily { CV_THIN_IN, CV_THIN_OUT, CV_HALO_L2, CV_HALO_LDS, CV_FRAME4, CV_FRAME8, CV_TAP };
+struct GroupKind { int rows, frames, side, tile_floats, slots; ConvFamily family; };
+constexpr int kGroupKinds = 5;
+constexpr GroupKind kGroupKind[kGroupKinds] = {
+    {256, 0, 16, 256 * BN, 64, CV_HALO_L2},      // 0: frames >= 16 pixels, two workgroups per CU
+    {128, 0, 8, 128 * BN, 96, CV_HALO_L2},       // 1: the same on 128-row tiles, three per CU
+    {256, 4, 8, 256 * BN, 64, CV_FRAME8},        // 2: whole 8 x 8 frames
+    {128, 2, 8, 128 * BN, 96, CV_FRAME8},        // 3
+    {128, 8, 4, 128 * BN, 96, CV_FRAME4},        // 4: whole 4 x 4 frames
+};
+
+// One row of a launch table: the instantiation that serves a plan's key (conv_igemm.hip: cv_launch).  f32 / ks / up2 are 0 in
+// the families whose kernels do not specialise on them.
+struct ConvRow { unsigned key; void (*kernel)(ConvK); };
+constexpr unsigned cv_key(ConvFamily family, int f32, int rows, int cols, int ks, int relu, int up2) {
+    return (unsigned)family | f32 << 3 | (rows / 64) << 4 | (cols / 64) << 7 | ks << 10 | relu << 13 | up2 << 14;
+}
+inline bool cv_launch_row(const ConvRow* rows, int n, unsigned key, const ConvK& p, dim3 grid, int threads, hipStream_t st) {
+    for (int i = 0; i < n; ++i) if (rows[i].key == key) { rows[i].kernel<<<grid, threads, 0, st>>>(p); return true; }
+    return false;                               // no such instantiation: nothing falls back
+}
+// conv_gb.hip: its rows (CV_HALO_L2, CV_FRAME4 / 8; 256 threads) and the grouped launch of kGroupKind[kind]
+bool launch_gb(unsigned key, const ConvK& p, dim3 grid, hipStream_t st);
 void launch_group(const ConvGroup& grp, int kind, hipStream_t st);
 
 }  // namespace dvdk

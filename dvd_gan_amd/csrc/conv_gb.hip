@@ -510,128 +510,49 @@ __global__ __launch_bounds__(256, 2) void conv_group_gbs_kernel(ConvGroup grp) {
     });
 }
 
-// standard forward pack [tap][Cout][C] (bf16) -> fragment-major [tap][chunk][nb32][kk][lane][8] (zeros in every padded position)
-struct FragK { const bf16_t* w; bf16_t* wq; int ntaps, Cout, C, kchunks, nb32; };
-__global__ void fragment_major_kernel(FragK p) {
-    const long long n = (long long)p.ntaps * p.kchunks * p.nb32 * 2 * 64;             // 16-byte units
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int l = (int)(i & 63);
-    long long r = i >> 6;
-    const int kk = (int)(r & 1); r >>= 1;
-    const int nb = (int)(r % p.nb32); r /= p.nb32;
-    const int cc = (int)(r % p.kchunks);
-    const int tap = (int)(r / p.kchunks);
-    const int co = nb * 32 + (l & 31), ci = cc * 32 + (kk * 2 + (l >> 5)) * 8;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (co < p.Cout && ci < p.C) v = *reinterpret_cast<const u32x4*>(p.w + ((size_t)tap * p.Cout + co) * p.C + ci);   // C % 8 == 0
-    *reinterpret_cast<u32x4*>(p.wq + i * 8) = v;
-}
-// n images in one launch (whole blocks per item, as pack_weight_batched_kernel)
-constexpr int kFragBatch = 32;
-struct FragBatchK { FragK it[kFragBatch]; int first[kFragBatch + 1]; int n; };
-__global__ void fragment_major_batched_kernel(FragBatchK b) {
-    int j = 0;
-    while (j + 1 < b.n && (int)blockIdx.x >= b.first[j + 1]) ++j;
-    const FragK& p = b.it[j];
-    const long long n = (long long)p.ntaps * p.kchunks * p.nb32 * 2 * 64;
-    const long long i = (long long)((int)blockIdx.x - b.first[j]) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int l = (int)(i & 63);
-    long long r = i >> 6;
-    const int kk = (int)(r & 1); r >>= 1;
-    const int nb = (int)(r % p.nb32); r /= p.nb32;
-    const int cc = (int)(r % p.kchunks);
-    const int tap = (int)(r / p.kchunks);
-    const int co = nb * 32 + (l & 31), ci = cc * 32 + (kk * 2 + (l >> 5)) * 8;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (co < p.Cout && ci < p.C) v = *reinterpret_cast<const u32x4*>(p.w + ((size_t)tap * p.Cout + co) * p.C + ci);
-    *reinterpret_cast<u32x4*>(p.wq + i * 8) = v;
-}
-
 }  // namespace
 
-// ---------------------------------------------------------------------------- launchers (called by conv_igemm.hip's dispatch / gru.hip)
+// ---------------------------------------------------------------------------- launch tables (conv_igemm.hip: cv_launch; gru.hip)
+namespace dvdk {
+#define GB(R, C, KS, RL, UP) cv_key(CV_HALO_L2, 0, R, C, KS, RL, UP)
+#define GBS(F, R, KS, RL) cv_key(F, 0, R, 128, KS, RL, 0)
+static const ConvRow kGbRows[] = {
 #ifdef DVD_GB_PROBE      // ISA inspection build (tools/isa_probe.sh): one instantiation of each kernel family
-namespace dvdk {
-void launch_gb(const ConvK& p, int, bool, bool, dim3 grid, hipStream_t st) { conv_halo_gb_kernel<4, 2, 2, false, false, 5><<<grid, 256, 0, st>>>(p); }
-void launch_gbs(const ConvK& p, int, bool, bool, dim3 grid, hipStream_t st) { conv_halo_gbs_kernel<2, 8, false, 3><<<grid, 256, 0, st>>>(p); }
-void launch_group(const ConvGroup& grp, int, hipStream_t st) { conv_group_gb_kernel<4, 2, 2><<<dim3(grp.nslots), 256, 0, st>>>(grp); }
-}
+    {GB(256, 128, 5, 0, 0), conv_halo_gb_kernel<4, 2, 2, false, false, 5>}, {GBS(CV_FRAME8, 128, 3, 0), conv_halo_gbs_kernel<2, 8, false, 3>},
 #else
-namespace dvdk {
-// variant: 0 = 256 x 128 tile, 1 = 128 x 128 (launches with few rows), 2 = 256 x 64 (thin outputs); p.kh == p.kw in {3, 5}
-void launch_gb(const ConvK& p, int variant, bool relu_in, bool up2, dim3 grid, hipStream_t st) {
-#define LAUNCH_GB4(TM_, WN_, WMV_, KS_)                                                                       \
-    do { if (relu_in) { if (up2) conv_halo_gb_kernel<TM_, WN_, WMV_, true, true, KS_><<<grid, 256, 0, st>>>(p);       \
-                        else conv_halo_gb_kernel<TM_, WN_, WMV_, true, false, KS_><<<grid, 256, 0, st>>>(p); }           \
-         else         { if (up2) conv_halo_gb_kernel<TM_, WN_, WMV_, false, true, KS_><<<grid, 256, 0, st>>>(p);      \
-                        else conv_halo_gb_kernel<TM_, WN_, WMV_, false, false, KS_><<<grid, 256, 0, st>>>(p); } } while (0)
-#define LAUNCH_GB(TM_, WN_, WMV_) do { if (p.kh == 5) LAUNCH_GB4(TM_, WN_, WMV_, 5); else LAUNCH_GB4(TM_, WN_, WMV_, 3); } while (0)
-    if (variant == 2) LAUNCH_GB(2, 1, 4); else if (variant == 0) LAUNCH_GB(4, 2, 2); else LAUNCH_GB(2, 2, 2);
-#undef LAUNCH_GB
-#undef LAUNCH_GB4
-}
-// whole-frame footprints: S = 8 (256- or 128-row tiles) or S = 4 (128-row tiles)
-void launch_gbs(const ConvK& p, int S, bool big, bool relu_in, dim3 grid, hipStream_t st) {
-#define LAUNCH_GBS2(TM_, SZ_, KS_) do { if (relu_in) conv_halo_gbs_kernel<TM_, SZ_, true, KS_><<<grid, 256, 0, st>>>(p);   \
-                                        else conv_halo_gbs_kernel<TM_, SZ_, false, KS_><<<grid, 256, 0, st>>>(p); } while (0)
-#define LAUNCH_GBS(TM_, SZ_) do { if (p.kh == 5) LAUNCH_GBS2(TM_, SZ_, 5); else LAUNCH_GBS2(TM_, SZ_, 3); } while (0)
-    if (S == 8) { if (big) LAUNCH_GBS(4, 8); else LAUNCH_GBS(2, 8); }
-    else LAUNCH_GBS(2, 4);
-#undef LAUNCH_GBS
-#undef LAUNCH_GBS2
-}
-// grouped launch: kind 0 = conv_halo_gb 256 x 128 tiles, 1 = conv_halo_gb 128 x 128, 2 / 3 = whole 8 x 8 frames 256- / 128-row tiles,
-// 4 = whole 4 x 4 frames (128-row tiles); every member: bf16, fragment-major weights, no input ReLU, no upsample
-void launch_group(const ConvGroup& grp, int kind, hipStream_t st) {
-    const dim3 grid(grp.nslots);
-    switch (kind) {
-        case 0: conv_group_gb_kernel<4, 2, 2><<<grid, 256, 0, st>>>(grp); break;
-        case 1: conv_group_gb_kernel<2, 2, 2><<<grid, 256, 0, st>>>(grp); break;
-        case 2: conv_group_gbs_kernel<4, 8><<<grid, 256, 0, st>>>(grp); break;
-        case 3: conv_group_gbs_kernel<2, 8><<<grid, 256, 0, st>>>(grp); break;
-        default: conv_group_gbs_kernel<2, 4><<<grid, 256, 0, st>>>(grp); break;
-    }
-}
-}  // namespace dvdk
+    // weights from L2, frames >= 16 pixels: 256 x 128, 128 x 128 (launches with few rows), 256 x 64 (thin outputs); relu_in 0 | 1
+    {GB(256, 128, 3, 0, 0), conv_halo_gb_kernel<4, 2, 2, false, false, 3>}, {GB(256, 128, 3, 1, 0), conv_halo_gb_kernel<4, 2, 2, true, false, 3>},
+    {GB(256, 128, 3, 0, 1), conv_halo_gb_kernel<4, 2, 2, false, true, 3>},  {GB(256, 128, 3, 1, 1), conv_halo_gb_kernel<4, 2, 2, true, true, 3>},
+    {GB(256, 128, 5, 0, 0), conv_halo_gb_kernel<4, 2, 2, false, false, 5>}, {GB(256, 128, 5, 1, 0), conv_halo_gb_kernel<4, 2, 2, true, false, 5>},
+    {GB(256, 128, 5, 0, 1), conv_halo_gb_kernel<4, 2, 2, false, true, 5>},  {GB(256, 128, 5, 1, 1), conv_halo_gb_kernel<4, 2, 2, true, true, 5>},
+    {GB(128, 128, 3, 0, 0), conv_halo_gb_kernel<2, 2, 2, false, false, 3>}, {GB(128, 128, 3, 1, 0), conv_halo_gb_kernel<2, 2, 2, true, false, 3>},
+    {GB(128, 128, 3, 0, 1), conv_halo_gb_kernel<2, 2, 2, false, true, 3>},  {GB(128, 128, 3, 1, 1), conv_halo_gb_kernel<2, 2, 2, true, true, 3>},
+    {GB(128, 128, 5, 0, 0), conv_halo_gb_kernel<2, 2, 2, false, false, 5>}, {GB(128, 128, 5, 1, 0), conv_halo_gb_kernel<2, 2, 2, true, false, 5>},
+    {GB(128, 128, 5, 0, 1), conv_halo_gb_kernel<2, 2, 2, false, true, 5>},  {GB(128, 128, 5, 1, 1), conv_halo_gb_kernel<2, 2, 2, true, true, 5>},
+    {GB(256, 64, 3, 0, 0), conv_halo_gb_kernel<2, 1, 4, false, false, 3>},  {GB(256, 64, 3, 1, 0), conv_halo_gb_kernel<2, 1, 4, true, false, 3>},
+    {GB(256, 64, 3, 0, 1), conv_halo_gb_kernel<2, 1, 4, false, true, 3>},   {GB(256, 64, 3, 1, 1), conv_halo_gb_kernel<2, 1, 4, true, true, 3>},
+    {GB(256, 64, 5, 0, 0), conv_halo_gb_kernel<2, 1, 4, false, false, 5>},  {GB(256, 64, 5, 1, 0), conv_halo_gb_kernel<2, 1, 4, true, false, 5>},
+    {GB(256, 64, 5, 0, 1), conv_halo_gb_kernel<2, 1, 4, false, true, 5>},   {GB(256, 64, 5, 1, 1), conv_halo_gb_kernel<2, 1, 4, true, true, 5>},
+    // whole-frame footprints: 8 x 8 frames on 256- or 128-row tiles, 4 x 4 frames on 128-row tiles
+    {GBS(CV_FRAME8, 256, 3, 0), conv_halo_gbs_kernel<4, 8, false, 3>},      {GBS(CV_FRAME8, 256, 3, 1), conv_halo_gbs_kernel<4, 8, true, 3>},
+    {GBS(CV_FRAME8, 256, 5, 0), conv_halo_gbs_kernel<4, 8, false, 5>},      {GBS(CV_FRAME8, 256, 5, 1), conv_halo_gbs_kernel<4, 8, true, 5>},
+    {GBS(CV_FRAME8, 128, 3, 0), conv_halo_gbs_kernel<2, 8, false, 3>},      {GBS(CV_FRAME8, 128, 3, 1), conv_halo_gbs_kernel<2, 8, true, 3>},
+    {GBS(CV_FRAME8, 128, 5, 0), conv_halo_gbs_kernel<2, 8, false, 5>},      {GBS(CV_FRAME8, 128, 5, 1), conv_halo_gbs_kernel<2, 8, true, 5>},
+    {GBS(CV_FRAME4, 128, 3, 0), conv_halo_gbs_kernel<2, 4, false, 3>},      {GBS(CV_FRAME4, 128, 3, 1), conv_halo_gbs_kernel<2, 4, true, 3>},
+    {GBS(CV_FRAME4, 128, 5, 0), conv_halo_gbs_kernel<2, 4, false, 5>},      {GBS(CV_FRAME4, 128, 5, 1), conv_halo_gbs_kernel<2, 4, true, 5>},
 #endif
-
-// Fragment-major image of a forward (or backward-data) pack for conv_halo_gb_kernel; see the comment at the top.
-extern "C" long long dvd_conv_fragment_major_bytes(int ntaps, int Cout, int C) {
-    if (ntaps <= 0 || Cout <= 0 || C <= 0) return 0;
-    const long long kchunks = (C + 31) / 32, nb32 = (Cout + 127) / 128 * 4;
-    return (long long)ntaps * kchunks * nb32 * 2048;
-}
-extern "C" int dvd_conv_fragment_major(int dtype, const void* w, void* wq, int ntaps, int Cout, int C, void* stream) {
-    if (!w || !wq || ntaps <= 0 || Cout <= 0 || C <= 0) return DVD_E_ARG;
-    if (dtype != DVD_BF16 || (C & 7)) return DVD_E_SHAPE;
-    FragK p{(const bf16_t*)w, (bf16_t*)wq, ntaps, Cout, C, (C + 31) / 32, (Cout + 127) / 128 * 4};
-    const long long n = (long long)ntaps * p.kchunks * p.nb32 * 128;
-    fragment_major_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(p);
-    return launch_status();
-}
-
-extern "C" int dvd_conv_fragment_major_batched(int dtype, const dvd_frag_item* items, int n, void* stream) {
-    if (!items || n <= 0) return DVD_E_ARG;
-    if (dtype != DVD_BF16) return DVD_E_SHAPE;
-    for (int i = 0; i < n; ++i) {
-        if (!items[i].w || !items[i].wq || items[i].ntaps <= 0 || items[i].Cout <= 0 || items[i].C <= 0) return DVD_E_ARG;
-        if (items[i].C & 7) return DVD_E_SHAPE;
-    }
-    for (int i0 = 0; i0 < n; i0 += kFragBatch) {
-        FragBatchK b;
-        b.n = n - i0 < kFragBatch ? n - i0 : kFragBatch;
-        long long blocks = 0;
-        for (int j = 0; j < b.n; ++j) {
-            const dvd_frag_item& t = items[i0 + j];
-            b.it[j] = FragK{(const bf16_t*)t.w, (bf16_t*)t.wq, t.ntaps, t.Cout, t.C, (t.C + 31) / 32, (t.Cout + 127) / 128 * 4};
-            b.first[j] = (int)blocks;
-            blocks += cdiv((long long)t.ntaps * b.it[j].kchunks * b.it[j].nb32 * 128, 256);
-        }
-        if (blocks >= (1ll << 31)) return DVD_E_SHAPE;
-        b.first[b.n] = (int)blocks;
-        fragment_major_batched_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(b);
-    }
-    return launch_status();
-}
+};
+#undef GB
+#undef GBS
+bool launch_gb(unsigned key, const ConvK& p, dim3 grid, hipStream_t st) { return cv_launch_row(kGbRows, (int)(sizeof kGbRows / sizeof kGbRows[0]), key, p, grid, 256, st); }
+// the kernel of kGroupKind[kind] (<rows / 64, 2, 2> | <rows / 64, side>); every member: bf16, fragment-major weights, no input ReLU, no upsample
+static void (*const kGroupKernel[])(ConvGroup) = {
+#ifdef DVD_GB_PROBE
+    conv_group_gb_kernel<4, 2, 2>, conv_group_gb_kernel<4, 2, 2>, conv_group_gb_kernel<4, 2, 2>, conv_group_gb_kernel<4, 2, 2>, conv_group_gb_kernel<4, 2, 2>,
+#else
+    conv_group_gb_kernel<4, 2, 2>, conv_group_gb_kernel<2, 2, 2>, conv_group_gbs_kernel<4, 8>, conv_group_gbs_kernel<2, 8>, conv_group_gbs_kernel<2, 4>,
+#endif
+};
+static_assert(sizeof kGroupKernel / sizeof kGroupKernel[0] == kGroupKinds, "one kernel per row of kGroupKind");
+void launch_group(const ConvGroup& grp, int kind, hipStream_t st) { kGroupKernel[kind]<<<dim3(grp.nslots), 256, 0, st>>>(grp); }
+}  // namespace dvdk

@@ -1,13 +1,12 @@
-// Convolutions of the DVD-GAN step for gfx950: forward / backward-data (implicit GEMM, no im2col) and
-// backward-weight, bf16 MFMA with fp32 accumulation or exact fp32 MFMA.
+// Convolutions of the DVD-GAN step for gfx950: forward / backward-data (implicit GEMM, no im2col),
+// bf16 MFMA with fp32 accumulation or exact fp32 MFMA.
 //
 //   conv_halo_kernel       3x3 / 5x5 / 3x3x3 filters on frames >= 16 pixels wide: the input footprint of a
 //                          16 x 16 pixel patch is staged in LDS once per channel chunk (LDS-DMA), every tap
 //                          reads it at an immediate offset; only the weight tile moves per tap.
 //   conv_igemm_kernel      1x1 filters and narrow frames: activation tile gathered per (chunk, tap).
-//   conv_wgrad_row_kernel  weight gradients, one filter row (all KW taps) per workgroup, reduction over pixels
-//                          through transposing LDS reads (ds_read_b64_tr_b16).
-//   conv_wgrad_kernel      weight gradients, one tap per workgroup (1x1, upsampling convs, fp32 mode).
+//   cv_plan / cv_launch    the planner of every forward / backward-data request and its launch table (also for the
+//                          kernels of conv_gb.hip and conv_thin.hip); weight gradients: conv_wgrad.hip, packs: conv_pack.hip.
 //
 //   bf16 : v_mfma_f32_32x32x16_bf16   (A: lane l holds row l&31, k = 8*(l>>5)..+7)
 //   f32  : v_mfma_f32_32x32x2_f32     (A: lane l holds row l&31, k = l>>5)        exact mode
@@ -262,7 +261,7 @@ __global__ __launch_bounds__(128 * WN) void conv_igemm_kernel(ConvK p) {
     // 6x slower) and turns the global stores into coalesced 16/32-byte vectors.
     float* ep = reinterpret_cast<float*>(&smem[0][0]) + wave * (32 * 64);
     const int ecol = (lane & 7) * 8, erow = lane >> 3;
-    if (p.pm) {          // rows of the tile are scattered over the tensor: offsets from its start (small tensors only, see conv_plan)
+    if (p.pm) {          // rows of the tile are scattered over the tensor: offsets from its start (small tensors only, see cv_choose_order)
         conv_epilogue<T, TM, 0, WN == 2>(p, acc, ep, lane, n0 + wn * 64 + ecol, z, (int)blockIdx.x, 0ll, [&](int tm, int j) __attribute__((always_inline)) {
             const int mp = m0 + wm * (TM * 32) + tm * 32 + j * 8 + erow;
             return mp < p.M ? memrow(mp) : -1;
@@ -559,132 +558,38 @@ __global__ __launch_bounds__(64 * WMV * WN, sizeof(T) == 2 ? 2 : 1) void conv_ha
     conv_halo_tile<T, TM, WN, RELU, UP2, WMV>(p, smem, mt, nt, blockIdx.z);
 }
 
-// ============================================================================ weight packing
-struct PackK {
-    const float* w; const float* sigma; char* wf; char* wd;
-    int Cout, Cin, ntaps, Cip, co_off, co_tot_f, co_tot_d, kt, kh, kw, ci_off, ci_tot;
-};
-// one thread per (co, ci_pad, tap) of the forward pack; writes both packs
-template <typename T>
-__global__ void pack_weight_kernel(PackK p) {
-    const long long n = (long long)p.Cout * p.Cip * p.ntaps;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int tap = (int)(i % p.ntaps);
-    const long long r = i / p.ntaps;
-    const int ci = (int)(r % p.Cip), co = (int)(r / p.Cip);
-    float v = 0.f;
-    if (ci < p.Cin) {
-        v = p.w[((size_t)co * p.ci_tot + p.ci_off + ci) * p.ntaps + tap];
-        if (p.sigma) v = v / *p.sigma;
-    }
-    if (p.wf) stf(reinterpret_cast<T*>(p.wf) + ((size_t)tap * p.co_tot_f + p.co_off + co) * p.Cip + ci, v);
-    if (p.wd) {
-        const int ftap = p.ntaps - 1 - tap;     // flipping every axis == reversing the flat tap index
-        stf(reinterpret_cast<T*>(p.wd) + ((size_t)ftap * p.Cip + ci) * p.co_tot_d + p.co_off + co, v);
-    }
-}
-
-// n packs in one launch: block b serves item j with first[j] <= b < first[j + 1] (whole blocks per item)
-constexpr int kPackBatch = 24;
-struct PackBatchK { PackK it[kPackBatch]; int first[kPackBatch + 1]; int n; };
-template <typename T>
-__global__ void pack_weight_batched_kernel(PackBatchK b) {
-    int j = 0;
-    while (j + 1 < b.n && (int)blockIdx.x >= b.first[j + 1]) ++j;
-    const PackK& p = b.it[j];
-    const long long n = (long long)p.Cout * p.Cip * p.ntaps;
-    const long long i = (long long)((int)blockIdx.x - b.first[j]) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int tap = (int)(i % p.ntaps);
-    const long long r = i / p.ntaps;
-    const int ci = (int)(r % p.Cip), co = (int)(r / p.Cip);
-    float v = 0.f;
-    if (ci < p.Cin) {
-        v = p.w[((size_t)co * p.ci_tot + p.ci_off + ci) * p.ntaps + tap];
-        if (p.sigma) v = v / *p.sigma;
-    }
-    if (p.wf) stf(reinterpret_cast<T*>(p.wf) + ((size_t)tap * p.co_tot_f + p.co_off + co) * p.Cip + ci, v);
-    if (p.wd) {
-        const int ftap = p.ntaps - 1 - tap;
-        stf(reinterpret_cast<T*>(p.wd) + ((size_t)ftap * p.Cip + ci) * p.co_tot_d + p.co_off + co, v);
-    }
-}
-
 }  // namespace
 
-// ============================================================================ optional profiling
-// bench.py needs the average duration of the dominant kernel measured with HIP events on the
-// launch stream.  When enabled, every conv launch is bracketed by an event pair; dvd_prof_report
-// synchronises and sums them.  Off by default (no events, no global state touched).
-#include <vector>
-#include <mutex>
-#include <cstdio>
-#include <cstdlib>
-namespace dvdprof {
-bool g_prof = false;
-std::vector<ProfRec> g_recs;
-std::mutex g_prof_mu;
-}  // namespace dvdprof
-using namespace dvdprof;
-extern "C" void dvd_prof_enable(int on) {
-    std::lock_guard<std::mutex> l(g_prof_mu);
-    g_prof = on != 0;
-}
-// kind 0 = conv_igemm (forward / backward-data), 1 = conv_wgrad.  Drains the records of `kind` and returns the number of
-// launches; n / ms / flops (each [nvar] or NULL) receive the per-variant totals -- kind 0: 1 = conv_halo 256 x 128,
-// 2 = conv_halo 128 x 128, 3 = conv_halo 256 x 64 (thin outputs), 4 = conv_igemm 128 x 128, 5 = conv_igemm 256 x 128,
-// 6 = conv_igemm 256 x 256 (8 waves), 7 / 8 = whole-frame footprint kernel (4 x 4 / 8 x 8 frames) 256 x 128 / 128 x 128, 9 = thin-input kernel (conv_thin.hip); kind 1: 1 = filter-row kernel, 2 = one-tap kernel, 3 = thin-end kernel (wgrad_thin.hip); index 0 = everything.
-// If the environment variable DVD_PROF_CSV is set, every drained record is appended to that file.
-extern "C" long long dvd_prof_report_variants(int kind, int nvar, long long* n, double* ms, double* flops) {
-    std::lock_guard<std::mutex> l(g_prof_mu);
-    for (int v = 0; v < nvar; ++v) { if (n) n[v] = 0; if (ms) ms[v] = 0; if (flops) flops[v] = 0; }
-    long long total = 0;
-    std::vector<ProfRec> keep;
-    const char* csv = getenv("DVD_PROF_CSV");
-    FILE* f = csv ? fopen(csv, "a") : nullptr;
-    for (auto& r : g_recs) {
-        if (r.kind != kind) { keep.push_back(r); continue; }
-        hipEventSynchronize(r.b);
-        float t = 0; hipEventElapsedTime(&t, r.a, r.b);
-        if (f) fprintf(f, "%d,%lld,%d,%d,%d,%d,%d,%.4f,%.0f,%d\n", r.kind, r.M, r.C, r.Cout, r.taps, r.split, r.flags, t, r.flops, r.variant);
-        const int slots[2] = {0, r.variant};                    // slot 0 = all launches, plus the record's own slot
-        for (int j = 0; j < (r.variant > 0 ? 2 : 1); ++j) {
-            const int v = slots[j];
-            if (v >= nvar) continue;
-            if (n) ++n[v];
-            if (ms) ms[v] += t;
-            if (flops) flops[v] += r.flops;
-        }
-        ++total;
-        hipEventDestroy(r.a); hipEventDestroy(r.b);
-    }
-    if (f) fclose(f);
-    g_recs.swap(keep);
-    return total;
-}
-extern "C" long long dvd_prof_report(int kind, double* total_ms, double* total_flops) {
-    long long n = 0;
-    return dvd_prof_report_variants(kind, 1, &n, total_ms, total_flops);
-}
+// ============================================================================ planner
+// A forward / backward-data request becomes ONE ConvPlan in three steps: cv_fill_request (validate, fill the kernel arguments),
+// cv_choose_kernel (kernel family and tile) and cv_choose_order (tile and row order); cv_plan then adds the grid, the profiling
+// variant and the FLOP count.  The entry points plan, then read a field or hand the plan to cv_launch.
+struct ConvPlan {
+    int rc;                                      // DVD_OK, or why there is no plan
+    const dvd_conv_desc* d;                      // the request (the thin kernels of conv_thin.hip take it as it is)
+    ConvK p;
+    long long M;                                 // output rows
+    ConvFamily family;
+    int rows, cols, threads;                     // tile: 128 / 256 rows x 64 / 128 / 256 columns (0 x 0: CV_THIN_*)
+    dim3 grid;                                   // (tiles, 1, K slices); the thin kernels size their own persistent grid
+    ConvVariant variant;
+    double flops;
+};
 
-// ============================================================================ C ABI
-extern "C" int dvd_conv_forward(const dvd_conv_desc* d, void* stream) { return dvd_conv_forward_gru(d, nullptr, stream); }
-
-// Validates a forward / backward-data request and derives the kernel parameters and the variant that serves it.
-struct ConvPlan { long long M; bool halo, thin, wide, big, smallf; };
-static int conv_plan(const dvd_conv_desc* d, const GruEpi* g, ConvK& p, ConvPlan& pl) {
-    if (!d || !d->in || !d->w || (!d->ws && (!d->out || (d->nsplit > 1 && !g)))) return DVD_E_ARG;
+// Step 1: validate the request and fill the kernel arguments that do not depend on the kernel.
+// geometry: a query (dvd_conv_wants_fragment_major, dvd_conv_pool2_ok) -- only the geometry matters, the buffers may not exist yet.
+static int cv_fill_request(const dvd_conv_desc* d, const GruEpi* g, bool geometry, ConvPlan& pl) {
+    if (!d || (!geometry && (!d->in || !d->w || (!d->ws && !d->out))) || (!d->ws && d->nsplit > 1 && !g)) return DVD_E_ARG;
     if (g && (d->ws || (g->h & 7) || (d->nsplit > 1 && (!g->slabs || !g->tickets)))) return DVD_E_ARG;
     if (d->frames <= 0 || d->T <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0 || d->Cout <= 0) return DVD_E_ARG;
     int logH = ilog2_exact(d->H), logW = ilog2_exact(d->W);
-    const bool pow2 = logH >= 0 && logW >= 0;
-    if (!pow2) logH = logW = -1;           // any other extent: division-based indexing in the tap-by-tap kernels (grid_pos)
+    if (logH < 0 || logW < 0) logH = logW = -1;   // any other extent: division-based indexing in the tap-by-tap kernels (grid_pos)
     if ((d->C & 7) || (d->ldi & 7) || !(d->kt & d->kh & d->kw & 1)) return DVD_E_SHAPE;
     if (d->up2 && ((d->H | d->W) & 1)) return DVD_E_SHAPE;
     if (d->kt > 1 && d->up2) return DVD_E_SHAPE;
     const long long M = (long long)d->frames * d->T * d->H * d->W;
     if (M >= (1ll << 31) - BM) return DVD_E_SHAPE;
+    ConvK& p = pl.p; pl.d = d; pl.M = M;
     p.in = (const char*)d->in; p.w = (const char*)d->w; p.bias = d->bias; p.res = (const char*)d->res;
     p.mask = (const char*)d->mask; p.out = (char*)d->out; p.ws = d->ws; p.wq = (const char*)d->wq;
     p.nb32 = (d->Cout + 127) / 128 * 4;
@@ -698,176 +603,183 @@ static int conv_plan(const dvd_conv_desc* d, const GruEpi* g, ConvK& p, ConvPlan
     p.kchunks = (d->C + bk - 1) / bk;
     p.nk = d->kt * d->kh * d->kw * p.kchunks;
     p.nsplit = d->nsplit < 1 ? 1 : d->nsplit;
-    if (p.nsplit > p.nk) p.nsplit = p.nk;
-    if (p.nsplit != (d->nsplit < 1 ? 1 : d->nsplit)) return DVD_E_ARG;   // caller sized ws for d->nsplit slabs
+    if (p.nsplit > p.nk) return DVD_E_ARG;        // caller sized ws for d->nsplit slabs
+    p.up2 = d->up2; p.relu_in = d->relu_in; p.act = d->act; p.out_f32 = d->out_f32; p.pool2 = d->pool2 != 0;
+    if (g) p.g = *g; else p.g = GruEpi{};
+    // extents of the two buffer descriptors (32-bit byte offsets): tensors must stay below 4 GiB
+    const size_t esz = d->dtype == DVD_BF16 ? 2 : 4;
+    const size_t rows_in = (size_t)d->frames * d->T * p.Hin * p.Win;
+    const size_t wb = (size_t)d->kt * d->kh * d->kw * d->Cout * d->C * esz;
+    if (wb >= 0xffffffffull) return DVD_E_SHAPE;
+    p.in_bytes = ((rows_in - 1) * (size_t)d->ldi + d->C) * esz; p.w_bytes = (unsigned)wb;
+    p.maxshift = ((d->kt >> 1) * d->H + (d->kh >> 1)) * d->W + (d->kw >> 1);
+    return DVD_OK;
+}
+
+// Step 2: the kernel family and its tile.  The rules are tested in this order: pool2, the thin ends, then the general kernels.
+static int cv_choose_kernel(const dvd_conv_desc* d, const GruEpi* g, bool geometry, ConvPlan& pl) {
+    ConvK& p = pl.p;
+    const long long M = pl.M;
+    const bool bf16 = d->dtype == DVD_BF16, pow2 = p.logW >= 0, square35 = d->kh == d->kw && (d->kh == 3 || d->kh == 5);
+    const bool image = geometry || d->wq;         // (a query asks "if the image were supplied")
+    // halo-staged kernel: square 3x3 / 5x5 (x3) filters on frames at least one 16 x 16 patch large.  It runs as
+    // 4-wave workgroups only: with the activation DMAs gone, two 256 x 128 workgroups per CU beat one 8-wave
+    // 256 x 256 workgroup (1.13-1.34 vs 0.86-1.12 PF/s on the S = 16 / 32 shapes of config C2).
+    const bool halo = pow2 && square35 && d->W >= 16 && d->H >= 16 && p.nsplit <= p.kchunks * d->kt;
+    // the 2 x 2 sums of a pool2 request are an epilogue of the halo-staged kernels' patch tiles (dvd_conv_pool2_ok)
+    if (p.pool2 && (!halo || p.nsplit != 1 || g || d->ws || d->res || d->act != DVD_ACT_NONE || d->kt != 1 || d->T != 1 || d->up2))
+        return DVD_E_SHAPE;
+    // the thin ends of the networks (conv_thin.hip: taps folded into K), given their own weight image.  A pool2 request never goes
+    // there: those kernels have no 2 x 2 sum epilogue and would write the full-size result into the half-size grid.  (This line owns
+    // the rule; dvd_conv_thin_*_ok repeat it for their own entry points dvd_conv_thin_in / dvd_conv_thin_out.)
+    const bool thin_in = !p.pool2 && dvd_conv_thin_in_ok(d), thin_out = !p.pool2 && dvd_conv_thin_out_ok(d);
+    const int wq_kind = geometry ? (thin_in ? 2 : thin_out ? 3 : 0) : d->wq_kind;
+    if (wq_kind >= 2 && !(wq_kind == 2 ? thin_in : thin_out)) return DVD_E_ARG;      // a thin image the request cannot use
+    if (!g && image && wq_kind == 2) { pl.family = CV_THIN_IN; return DVD_OK; }      // the stems / the RGB layer's backward-data pass
+    if (!g && image && wq_kind == 3) { pl.family = CV_THIN_OUT; return DVD_OK; }     // the RGB layer / the stems' backward-data pass
+    // frames of 4 x 4 / 8 x 8 pixels (bf16, 2-D taps, no upsample): whole-frame footprints in LDS, weights from L2 -- needs the
+    // fragment-major image
+    const bool smallf = !halo && pow2 && bf16 && image && d->kt == 1 && d->T == 1 && !d->up2 && square35 && d->H == d->W &&
+                        (d->W == 4 || d->W == 8) && p.nsplit <= p.kchunks && M < (1ll << 24);
+    // 256 x 64 tile for thin outputs of the halo-staged kernels
+    const bool narrow = halo && bf16 && d->Cout <= 64 && cdiv(M, 256) * (long long)p.nsplit >= 512;
     // 8-wave 256 x 256 tile when the output is wide enough (no more than 1/8 of the last N tile wasted)
     // and there is at least one tile per CU; else 256 x 128 (>= 2 tiles per CU) or 128 x 128.
     const long long t256 = cdiv(M, 256) * (long long)cdiv(d->Cout, 256) * p.nsplit;
     const int rem256 = d->Cout % 256;
-    // halo-staged kernel: square 3x3 / 5x5 (x3) filters on frames at least one 16 x 16 patch large.  It runs as
-    // 4-wave workgroups only: with the activation DMAs gone, two 256 x 128 workgroups per CU beat one 8-wave
-    // 256 x 256 workgroup (1.13-1.34 vs 0.86-1.12 PF/s on the S = 16 / 32 shapes of config C2).
-    const bool halo = pow2 && d->kh == d->kw && (d->kh == 3 || d->kh == 5) && d->W >= 16 && d->H >= 16 &&
-                      p.nsplit <= p.kchunks * d->kt;
-    // frames of 4 x 4 / 8 x 8 pixels (bf16, 2-D taps, no upsample): whole-frame footprints in LDS, weights from L2 -- needs the
-    // fragment-major image
-    const bool smallf = !halo && pow2 && d->dtype == DVD_BF16 && d->wq && d->kt == 1 && d->T == 1 && !d->up2 &&
-                        d->kh == d->kw && (d->kh == 3 || d->kh == 5) && d->H == d->W && (d->W == 4 || d->W == 8) &&
-                        p.nsplit <= p.kchunks && M < (1ll << 24);
-    const bool thin = halo && d->dtype == DVD_BF16 && d->Cout <= 64 && cdiv(M, 256) * (long long)p.nsplit >= 512;
-    const bool wide = !halo && !smallf && d->dtype == DVD_BF16 && d->Cout >= 256 && (rem256 == 0 || rem256 > 224) && t256 >= 256 &&
-                      !(g && p.nsplit > 1);
-    p.tilesN = wide ? (d->Cout + 255) / 256 : thin ? 1 : (d->Cout + BN - 1) / BN;
-    p.up2 = d->up2; p.relu_in = d->relu_in; p.act = d->act; p.out_f32 = d->out_f32;
-    if (g) p.g = *g; else p.g = GruEpi{};
-    p.nmajor = 0;
-    {   // extents of the two buffer descriptors (32-bit byte offsets): tensors must stay below 4 GiB
-        const size_t esz = d->dtype == DVD_BF16 ? 2 : 4;
-        const size_t rows_in = (size_t)d->frames * d->T * p.Hin * p.Win;
-        const size_t inb = ((rows_in - 1) * (size_t)d->ldi + d->C) * esz;
-        const size_t wb = (size_t)d->kt * d->kh * d->kw * d->Cout * d->C * esz;
-        if (wb >= 0xffffffffull) return DVD_E_SHAPE;
-        p.in_bytes = inb; p.w_bytes = (unsigned)wb;
-        p.maxshift = ((d->kt >> 1) * d->H + (d->kh >> 1)) * d->W + (d->kw >> 1);
-        p.nmajor = !halo && wb > inb && wb > (4u << 20);      // weights beyond one L2 (also for the small-frame halo kernel)
-        // halo kernel: with several N tiles and weights well beyond one L2, a run of workgroups that shares the weight tile
-        // (and streams the activations once per N tile) misses less than one that shares the footprint and cycles through
-        // all the weights: 1272 -> 1355 TF/s on 786 k x 256 -> 1536 (19.7 MB of weights); neutral from 5 MiB, -1.5 % at 4.9 MB
-        if (halo && p.tilesN > 1 && wb > ((size_t)5 << 20)) p.nmajor = 1;
-        if (halo && p.tilesN >= 6 && wb > (2u << 20)) p.nmajor = 1;      // 3.1 M x 128 -> 768 (4.9 MB, 6 N tiles): +2 %
-    }
+    const bool wide = !halo && !smallf && bf16 && d->Cout >= 256 && (rem256 == 0 || rem256 > 224) && t256 >= 256 && !(g && p.nsplit > 1);
+    pl.cols = wide ? 256 : narrow ? 64 : BN;
+    p.tilesN = (d->Cout + pl.cols - 1) / pl.cols;
     // 256-row tiles when they still give every CU work; 128-row tiles for the small recurrent convs
     constexpr long long big_thr = 512;          // (swept 128 / 256 / 512)
     // 1 x 1 filters are HBM-bound streams with 2-8 K steps: the 256-row tap-by-tap tile holds 433 registers = ONE workgroup per CU, the
     // 128-row tile 240 = two.  3.1 M x 128 -> 128: 665 -> 505 us, 128 -> 64: 691 -> 420, 64 -> 128: 574 -> 422; step 493.4 -> 490.9 ms
     const bool one_tap = d->kt * d->kh * d->kw == 1 && !halo && !smallf;
     const bool big = wide || (cdiv(M, 256) * (long long)p.tilesN * p.nsplit >= big_thr && !one_tap);   // >= 2 workgroups per CU
-    p.pm = 0;
-    {   // pixel-major row order for the tap-by-tap kernel on small frames: the rows of a tile must share their image line
-        const int bmt = (wide || big) ? 256 : 128;
-        const int F = d->frames;
-        const bool lines = (F % bmt == 0) || (bmt % F == 0 && d->W % (bmt / F) == 0);
-        const size_t esz = d->dtype == DVD_BF16 ? 2 : 4;
-        if (!halo && !smallf && pow2 && d->kt == 1 && d->T == 1 && !d->up2 && d->kh >= 3 && d->H <= 8 && lines &&
-            (size_t)M * (size_t)(d->ldi > 3 * d->Cout ? d->ldi : 3 * d->Cout) * 4 < (1ull << 31))     // every epilogue offset from row 0 fits
-            p.pm = F;
-    }
-    pl.M = M; pl.halo = halo; pl.thin = thin; pl.wide = wide; pl.big = big && !(smallf && d->W == 4); pl.smallf = smallf;
-    p.pool2 = d->pool2 != 0;
-    if (p.pool2 && (!halo || p.nsplit != 1 || g || d->ws || d->res || d->act != DVD_ACT_NONE || d->kt != 1 || d->T != 1 || d->up2))
-        return DVD_E_SHAPE;                   // (dvd_conv_pool2_ok: the 2 x 2 sums are an epilogue of the halo-staged kernels' patch tiles)
+    pl.rows = (big && !(smallf && d->W == 4)) ? 256 : 128;           // (4 x 4 frames: 128-row tiles only)
+    pl.threads = wide ? 512 : 256;
+    pl.family = halo ? (bf16 && image ? CV_HALO_L2 : CV_HALO_LDS)    // weights straight from L2 when the fragment-major image is supplied
+              : smallf ? (d->W == 4 ? CV_FRAME4 : CV_FRAME8) : CV_TAP;
     return DVD_OK;
 }
 
-extern "C" int dvd_conv_pool2_ok(const dvd_conv_desc* d) {
-    if (!d || !d->pool2) return 0;
-    ConvK p; ConvPlan pl;
-    dvd_conv_desc t = *d;
-    static char dummy;
-    if (!t.out) t.out = &dummy;               // (a geometry query: the output may not exist yet)
-    return conv_plan(&t, nullptr, p, pl) == DVD_OK ? 1 : 0;
+// Step 3: the order of the tiles in the grid (nmajor) and of the rows in a tile (pm).
+static void cv_choose_order(const dvd_conv_desc* d, ConvPlan& pl) {
+    ConvK& p = pl.p;
+    const bool halo = pl.family == CV_HALO_L2 || pl.family == CV_HALO_LDS;
+    const size_t wb = p.w_bytes;
+    p.nmajor = !halo && wb > p.in_bytes && wb > (4u << 20);      // weights beyond one L2 (also for the small-frame halo kernel)
+    // halo kernel: with several N tiles and weights well beyond one L2, a run of workgroups that shares the weight tile
+    // (and streams the activations once per N tile) misses less than one that shares the footprint and cycles through
+    // all the weights: 1272 -> 1355 TF/s on 786 k x 256 -> 1536 (19.7 MB of weights); neutral from 5 MiB, -1.5 % at 4.9 MB
+    if (halo && p.tilesN > 1 && wb > ((size_t)5 << 20)) p.nmajor = 1;
+    if (halo && p.tilesN >= 6 && wb > (2u << 20)) p.nmajor = 1;      // 3.1 M x 128 -> 768 (4.9 MB, 6 N tiles): +2 %
+    // pixel-major row order for the tap-by-tap kernel on small frames: the rows of a tile must share their image line
+    const int F = d->frames, bmt = pl.rows;
+    const bool lines = (F % bmt == 0) || (bmt % F == 0 && d->W % (bmt / F) == 0);
+    if (pl.family == CV_TAP && p.logW >= 0 && d->kt == 1 && d->T == 1 && !d->up2 && d->kh >= 3 && d->H <= 8 && lines &&
+        (size_t)pl.M * (size_t)(d->ldi > 3 * d->Cout ? d->ldi : 3 * d->Cout) * 4 < (1ull << 31))     // every epilogue offset from row 0 fits
+        p.pm = F;
 }
 
+static ConvPlan cv_plan(const dvd_conv_desc* d, const GruEpi* g, bool geometry = false) {
+    ConvPlan pl{};
+    pl.rc = cv_fill_request(d, g, geometry, pl);
+    if (pl.rc == DVD_OK) pl.rc = cv_choose_kernel(d, g, geometry, pl);
+    if (pl.rc != DVD_OK) return pl;
+    pl.flops = 2.0 * (double)pl.M * d->Cout * d->C * d->kt * d->kh * d->kw;
+    if (pl.family == CV_THIN_IN || pl.family == CV_THIN_OUT) { pl.variant = CV_VAR_THIN; return pl; }
+    cv_choose_order(d, pl);
+    pl.grid = dim3(cdiv(pl.M, pl.rows) * pl.p.tilesN, 1, pl.p.nsplit);      // (whole-frame tiles: rows / S^2 frames each, the same count)
+    pl.variant = pl.family == CV_TAP ? (pl.cols == 256 ? CV_VAR_TAP_256x256 : pl.rows == 256 ? CV_VAR_TAP_256x128 : CV_VAR_TAP_128x128)
+               : pl.family == CV_FRAME4 || pl.family == CV_FRAME8 ? (pl.rows == 256 ? CV_VAR_FRAME_256 : CV_VAR_FRAME_128)
+               : pl.cols == 64 ? CV_VAR_HALO_256x64 : pl.rows == 256 ? CV_VAR_HALO_256x128 : CV_VAR_HALO_128x128;
+    return pl;
+}
+
+// ============================================================================ dispatch
+// The instantiation that serves a plan, from a flat table keyed by (family, f32, tile, filter size, relu_in, up2); conv_gb.hip holds
+// the rows of the kernels that read their weights from L2.  A miss (another dtype, a planner bug) is DVD_E_ARG: nothing falls back.
+#define HALO(F32, R, C, RL, UP) cv_key(CV_HALO_LDS, F32, R, C, 0, RL, UP)
+#define TAP(F32, R, C, RL) cv_key(CV_TAP, F32, R, C, 0, RL, 0)
+static const ConvRow kConvRows[] = {
+    // halo-staged, weights through LDS: relu_in 0 | 1, then the same with the nearest-x2 upsample folded in
+    {HALO(0, 256, 128, 0, 0), conv_halo_kernel<bf16_t, 4, 2, false, false>},   {HALO(0, 256, 128, 1, 0), conv_halo_kernel<bf16_t, 4, 2, true, false>},
+    {HALO(0, 256, 128, 0, 1), conv_halo_kernel<bf16_t, 4, 2, false, true>},    {HALO(0, 256, 128, 1, 1), conv_halo_kernel<bf16_t, 4, 2, true, true>},
+    {HALO(0, 128, 128, 0, 0), conv_halo_kernel<bf16_t, 2, 2, false, false>},   {HALO(0, 128, 128, 1, 0), conv_halo_kernel<bf16_t, 2, 2, true, false>},
+    {HALO(0, 128, 128, 0, 1), conv_halo_kernel<bf16_t, 2, 2, false, true>},    {HALO(0, 128, 128, 1, 1), conv_halo_kernel<bf16_t, 2, 2, true, true>},
+    {HALO(0, 256, 64, 0, 0), conv_halo_kernel<bf16_t, 2, 1, false, false, 4>}, {HALO(0, 256, 64, 1, 0), conv_halo_kernel<bf16_t, 2, 1, true, false, 4>},
+    {HALO(0, 256, 64, 0, 1), conv_halo_kernel<bf16_t, 2, 1, false, true, 4>},  {HALO(0, 256, 64, 1, 1), conv_halo_kernel<bf16_t, 2, 1, true, true, 4>},
+    {HALO(1, 256, 128, 0, 0), conv_halo_kernel<float, 4, 2, false, false>},    {HALO(1, 256, 128, 1, 0), conv_halo_kernel<float, 4, 2, true, false>},
+    {HALO(1, 256, 128, 0, 1), conv_halo_kernel<float, 4, 2, false, true>},     {HALO(1, 256, 128, 1, 1), conv_halo_kernel<float, 4, 2, true, true>},
+    {HALO(1, 128, 128, 0, 0), conv_halo_kernel<float, 2, 2, false, false>},    {HALO(1, 128, 128, 1, 0), conv_halo_kernel<float, 2, 2, true, false>},
+    {HALO(1, 128, 128, 0, 1), conv_halo_kernel<float, 2, 2, false, true>},     {HALO(1, 128, 128, 1, 1), conv_halo_kernel<float, 2, 2, true, true>},
+    // tap-by-tap (the upsample is a run-time flag of this kernel); 256 x 256: 8 waves
+    {TAP(0, 256, 256, 0), conv_igemm_kernel<bf16_t, 4, 4, false>},             {TAP(0, 256, 256, 1), conv_igemm_kernel<bf16_t, 4, 4, true>},
+    {TAP(0, 256, 128, 0), conv_igemm_kernel<bf16_t, 4, 2, false>},             {TAP(0, 256, 128, 1), conv_igemm_kernel<bf16_t, 4, 2, true>},
+    {TAP(0, 128, 128, 0), conv_igemm_kernel<bf16_t, 2, 2, false>},             {TAP(0, 128, 128, 1), conv_igemm_kernel<bf16_t, 2, 2, true>},
+    {TAP(1, 256, 128, 0), conv_igemm_kernel<float, 4, 2, false>},              {TAP(1, 256, 128, 1), conv_igemm_kernel<float, 4, 2, true>},
+    {TAP(1, 128, 128, 0), conv_igemm_kernel<float, 2, 2, false>},              {TAP(1, 128, 128, 1), conv_igemm_kernel<float, 2, 2, true>},
+};
+#undef HALO
+#undef TAP
+
+static int cv_launch(const ConvPlan& pl, void* stream) {
+    const dvd_conv_desc* d = pl.d;
+    if (pl.family == CV_THIN_IN) return dvd_conv_thin_in(d, stream);
+    if (pl.family == CV_THIN_OUT) return dvd_conv_thin_out(d, stream);
+    if (d->dtype != DVD_BF16 && d->dtype != DVD_F32) return DVD_E_ARG;
+    const bool gb = pl.family != CV_HALO_LDS && pl.family != CV_TAP;        // conv_gb.hip's kernels specialise on the filter size
+    const unsigned key = cv_key(pl.family, d->dtype == DVD_F32, pl.rows, pl.cols, gb ? d->kh : 0, d->relu_in != 0,
+                                pl.family == CV_HALO_L2 || pl.family == CV_HALO_LDS ? d->up2 != 0 : 0);
+    const bool found = gb ? launch_gb(key, pl.p, pl.grid, (hipStream_t)stream)
+                          : cv_launch_row(kConvRows, (int)(sizeof kConvRows / sizeof kConvRows[0]), key, pl.p, pl.grid, pl.threads, (hipStream_t)stream);
+    return found ? launch_status() : DVD_E_ARG;
+}
+
+// ============================================================================ C ABI
+extern "C" int dvd_conv_forward(const dvd_conv_desc* d, void* stream) { return dvd_conv_forward_gru(d, nullptr, stream); }
+
 extern "C" int dvd_conv_forward_gru(const dvd_conv_desc* d, const GruEpi* g, void* stream) {
-    ConvK p; ConvPlan pl;
-    const int rc = conv_plan(d, g, p, pl);
-    if (rc != DVD_OK) return rc;
-    const long long M = pl.M;
-    const bool halo = pl.halo, thin = pl.thin, wide = pl.wide, big = pl.big;
-    if (d->wq_kind >= 2 && !(d->wq_kind == 2 ? dvd_conv_thin_in_ok(d) : dvd_conv_thin_out_ok(d))) return DVD_E_ARG;   // a thin image the request cannot use
-    if (d->wq_kind >= 2 && d->pool2) return DVD_E_ARG;   // the thin kernels would write the full-size result into the half-size grid
-    if (!g && d->wq && d->wq_kind == 2 && dvd_conv_thin_in_ok(d)) {      // the stems / the RGB layer's backward-data pass: taps folded into K (conv_thin.hip)
-        ProfScope prof(0, 2.0 * (double)M * d->Cout * d->C * d->kt * d->kh * d->kw, stream, M, d->C, d->Cout, d->kt * d->kh * d->kw, 1,
-                       d->relu_in << 1);
-        prof.r.variant = 9;
-        return dvd_conv_thin_in(d, stream);
-    }
-    if (!g && d->wq && d->wq_kind == 3 && dvd_conv_thin_out_ok(d)) {     // the RGB layer / the stems' backward-data pass (conv_thin.hip)
-        ProfScope prof(0, 2.0 * (double)M * d->Cout * d->C * d->kt * d->kh * d->kw, stream, M, d->C, d->Cout, d->kt * d->kh * d->kw, 1,
-                       d->relu_in << 1);
-        prof.r.variant = 9;
-        return dvd_conv_thin_out(d, stream);
-    }
-    dim3 grid(cdiv(M, big ? 256 : 128) * p.tilesN, 1, p.nsplit);
-    if (g && p.nsplit > 1 && grid.x > DVD_GRU_TICKETS) return DVD_E_SHAPE;      // one ticket per output tile (the small-frame grid below is no larger)
-    ProfScope prof(0, 2.0 * (double)M * d->Cout * d->C * d->kt * d->kh * d->kw, stream, M, d->C, d->Cout,
-                   d->kt * d->kh * d->kw, p.nsplit, d->up2 | (d->relu_in << 1) | ((d->ws != nullptr) << 2));
-    hipStream_t st = (hipStream_t)stream;
-    prof.r.variant = halo ? (thin ? 3 : big ? 1 : 2) : pl.smallf ? (big ? 7 : 8) : (wide ? 6 : big ? 5 : 4);
-    if (pl.smallf) {
-        const int S_ = d->W, Gf = (big ? 256 : 128) / (S_ * S_);
-        grid = dim3(cdiv(d->frames, Gf) * p.tilesN, 1, p.nsplit);
-        launch_gbs(p, S_, big, d->relu_in != 0, grid, st);
-        return launch_status();
-    }
-    if (halo) {
-#define LAUNCH_HALO2(TT, TM_, WN_, RL_)                                                             \
-        do { if (d->up2) conv_halo_kernel<TT, TM_, WN_, RL_, true><<<grid, 128 * WN_, 0, st>>>(p);      \
-             else conv_halo_kernel<TT, TM_, WN_, RL_, false><<<grid, 128 * WN_, 0, st>>>(p); } while (0)
-#define LAUNCH_HALO(TT, TM_, WN_)                                                                   \
-        do { if (d->relu_in) LAUNCH_HALO2(TT, TM_, WN_, true); else LAUNCH_HALO2(TT, TM_, WN_, false); } while (0)
-        if (d->dtype == DVD_BF16 && p.wq) {           // weights straight from L2 (fragment-major image supplied)
-            launch_gb(p, thin ? 2 : big ? 0 : 1, d->relu_in != 0, d->up2 != 0, grid, st);
-            return launch_status();
-        }
-        if (thin) {
-            if (d->relu_in) { if (d->up2) conv_halo_kernel<bf16_t, 2, 1, true, true, 4><<<grid, 256, 0, st>>>(p);
-                              else conv_halo_kernel<bf16_t, 2, 1, true, false, 4><<<grid, 256, 0, st>>>(p); }
-            else            { if (d->up2) conv_halo_kernel<bf16_t, 2, 1, false, true, 4><<<grid, 256, 0, st>>>(p);
-                              else conv_halo_kernel<bf16_t, 2, 1, false, false, 4><<<grid, 256, 0, st>>>(p); }
-        } else if (d->dtype == DVD_BF16) { if (big) LAUNCH_HALO(bf16_t, 4, 2); else LAUNCH_HALO(bf16_t, 2, 2); }
-        else if (d->dtype == DVD_F32) { if (big) LAUNCH_HALO(float, 4, 2); else LAUNCH_HALO(float, 2, 2); }
-        else return DVD_E_ARG;
-#undef LAUNCH_HALO
-#undef LAUNCH_HALO2
-        return launch_status();
-    }
-#define LAUNCH_CONV(TT)                                                                       \
-    do {                                                                                      \
-        if (big) { if (d->relu_in) conv_igemm_kernel<TT, 4, 2, true><<<grid, NT, 0, st>>>(p);   \
-                   else conv_igemm_kernel<TT, 4, 2, false><<<grid, NT, 0, st>>>(p); }           \
-        else     { if (d->relu_in) conv_igemm_kernel<TT, 2, 2, true><<<grid, NT, 0, st>>>(p);   \
-                   else conv_igemm_kernel<TT, 2, 2, false><<<grid, NT, 0, st>>>(p); }           \
-    } while (0)
-    if (wide) {
-        if (d->relu_in) conv_igemm_kernel<bf16_t, 4, 4, true><<<grid, 512, 0, st>>>(p);
-        else conv_igemm_kernel<bf16_t, 4, 4, false><<<grid, 512, 0, st>>>(p);
-    } else if (d->dtype == DVD_BF16) LAUNCH_CONV(bf16_t);
-    else if (d->dtype == DVD_F32) LAUNCH_CONV(float);
-    else return DVD_E_ARG;
-#undef LAUNCH_CONV
-    return launch_status();
+    const ConvPlan pl = cv_plan(d, g);
+    if (pl.rc != DVD_OK) return pl.rc;
+    if (g && pl.p.nsplit > 1 && pl.grid.x > DVD_GRU_TICKETS) return DVD_E_SHAPE;      // one ticket per output tile
+    ProfScope prof(0, pl.flops, stream, pl.M, d->C, d->Cout, d->kt * d->kh * d->kw, pl.p.nsplit,
+                   d->up2 | (d->relu_in << 1) | ((d->ws != nullptr) << 2));
+    prof.r.variant = pl.variant;
+    return cv_launch(pl, stream);
+}
+extern "C" int dvd_conv_pool2_ok(const dvd_conv_desc* d) { return d && d->pool2 && cv_plan(d, nullptr, true).rc == DVD_OK; }
+
+// 0, or the weight image dvd_conv_forward wants in d->wq for this request: 1 = the fragment-major image, 2 = dvd_conv_thin_image
+// (3 (8) input channels -> 64), 3 = dvd_conv_thin_out_image (64 -> 3 (8) channels)
+extern "C" int dvd_conv_wants_fragment_major(const dvd_conv_desc* d) {
+    const ConvPlan pl = cv_plan(d, nullptr, true);
+    if (pl.rc != DVD_OK) return 0;
+    return pl.family == CV_THIN_IN ? 2 : pl.family == CV_THIN_OUT ? 3 : (pl.family == CV_HALO_LDS || pl.family == CV_TAP) ? 0 : 1;
 }
 
 // Several INDEPENDENT convolutions in one launch (conv_gb.hip: group_dispatch; gru.hip: the layer wavefront of a ConvGRU stack).
 // Every member: bf16, fragment-major weights supplied (d[i].wq), square 3 x 3 / 5 x 5 taps, no input ReLU / upsample, all served by
-// the ONE kernel `kind` names (0 / 1 = conv_halo_gb 256 x 128 / 128 x 128 tiles: frames >= 16 pixels; 2 / 3 = whole 8 x 8 frames,
-// 256- / 128-row tiles; 4 = whole 4 x 4 frames).  g[i].mode: 0 = direct epilogue, 1-5 = ConvGRU gate epilogues, 6 = direct epilogue
-// behind an in-launch split-K combine; nsplit > 1 needs mode != 0 (g[i].slabs; g[i].tickets = the stream's ticket buffer: member i
+// the ONE kernel `kind` names (kGroupKind, conv_common.h).  g[i].mode: 0 = direct epilogue, 1-5 = ConvGRU gate epilogues, 6 = direct
+// epilogue behind an in-launch split-K combine; nsplit > 1 needs mode != 0 (g[i].slabs; g[i].tickets = the stream's ticket buffer: member i
 // takes counters [i * 1024, (i + 1) * 1024)).  run: ConvGroup::head, workgroups of the two longest members an XCD starts with (<= 0: 32).
 extern "C" int dvd_conv_forward_group(const dvd_conv_desc* d, const GruEpi* g, int n, int kind, int run, void* stream) {
-    if (!d || !g || n < 1 || n > kGroupMax || kind < 0 || kind > 4) return DVD_E_ARG;
+    if (!d || !g || n < 1 || n > kGroupMax || kind < 0 || kind >= kGroupKinds) return DVD_E_ARG;
+    const GroupKind& gk = kGroupKind[kind];
     ConvGroup grp = {};
     grp.n = n;
     double flops = 0; long long Msum = 0;
     for (int i = 0; i < n; ++i) {
-        ConvPlan pl;
         const GruEpi* gi = g[i].mode ? &g[i] : nullptr;
-        const int rc = conv_plan(&d[i], gi, grp.c[i], pl);
-        if (rc != DVD_OK) return rc;
-        ConvK& p = grp.c[i];
+        const ConvPlan pl = cv_plan(&d[i], gi);
+        if (pl.rc != DVD_OK) return pl.rc;
+        ConvK& p = grp.c[i] = pl.p;
         if (d[i].dtype != DVD_BF16 || !p.wq || d[i].wq_kind > 1 || d[i].relu_in || d[i].up2 || d[i].ws) return DVD_E_ARG;
-        long long mtiles;
-        if (kind <= 1) {
-            if (!pl.halo || d[i].H < (kind == 0 ? 16 : 8)) return DVD_E_SHAPE;
-            mtiles = cdiv(pl.M, kind == 0 ? 256 : 128);
-        } else {
-            const int S = kind == 4 ? 4 : 8;
-            if (!pl.smallf || d[i].W != S) return DVD_E_SHAPE;
-            mtiles = cdiv(d[i].frames, kind == 2 ? 4 : kind == 3 ? 2 : 8);
-        }
+        // the member's own plan must name the family of `kind`, on frames of its side (CV_HALO_L2: at least)
+        if (pl.family != gk.family || (gk.frames ? d[i].W != gk.side : d[i].H < gk.side)) return DVD_E_SHAPE;
         p.tilesN = (d[i].Cout + BN - 1) / BN;
-        const long long tiles = mtiles * p.tilesN;
+        const long long tiles = (long long)cdiv(pl.M, gk.rows) * p.tilesN;
         if (p.nsplit > 1) {
             if (!gi || tiles > 1024) return DVD_E_SHAPE;
             p.g.tickets += i * 1024;
@@ -878,75 +790,15 @@ extern "C" int dvd_conv_forward_group(const dvd_conv_desc* d, const GruEpi* g, i
         Msum += pl.M;
     }
     // slot order (ConvGroup): members by decreasing K length of a workgroup
-    {
-        long long len[kGroupMax];
-        for (int i = 0; i < n; ++i) { grp.order[i] = i; len[i] = (long long)grp.c[i].kchunks * d[i].kh * d[i].kw / grp.c[i].nsplit; }
-        for (int i = 1; i < n; ++i)
-            for (int j = i; j > 0 && len[grp.order[j]] > len[grp.order[j - 1]]; --j) { const int t = grp.order[j]; grp.order[j] = grp.order[j - 1]; grp.order[j - 1] = t; }
-        long long slots = 0;
-        for (int i = 0; i < n; ++i) slots += (grp.wgs[i] + 7) / 8;
-        grp.nslots = (int)(8 * slots);
-        grp.head = run > 0 ? run : run < 0 ? 0 : 32;
-    }
+    long long len[kGroupMax], slots = 0;
+    for (int i = 0; i < n; ++i) { grp.order[i] = i; len[i] = (long long)grp.c[i].kchunks * d[i].kh * d[i].kw / grp.c[i].nsplit; }
+    for (int i = 1; i < n; ++i)
+        for (int j = i; j > 0 && len[grp.order[j]] > len[grp.order[j - 1]]; --j) { const int t = grp.order[j]; grp.order[j] = grp.order[j - 1]; grp.order[j - 1] = t; }
+    for (int i = 0; i < n; ++i) slots += (grp.wgs[i] + 7) / 8;
+    grp.nslots = (int)(8 * slots);
+    grp.head = run > 0 ? run : run < 0 ? 0 : 32;
     ProfScope prof(0, flops, stream, Msum, d[0].C, d[0].Cout, d[0].kh * d[0].kw, n, 0);
-    prof.r.variant = kind <= 1 ? 10 : 11;
+    prof.r.variant = gk.family == CV_HALO_L2 ? CV_VAR_GROUP_HALO : CV_VAR_GROUP_FRAME;
     launch_group(grp, kind, (hipStream_t)stream);
-    return launch_status();
-}
-
-// 1 when dvd_conv_forward would run this request through the kernel that reads a fragment-major weight image (d->wq)
-extern "C" int dvd_conv_wants_fragment_major(const dvd_conv_desc* d) {
-    ConvK p; ConvPlan pl;
-    dvd_conv_desc t = *d;
-    if (!t.w) t.w = t.in;                 // (only the geometry matters here)
-    t.wq = t.w;                           // "if the image were supplied"
-    if (conv_plan(&t, nullptr, p, pl) != DVD_OK) return 0;
-    if (dvd_conv_thin_in_ok(d)) return 2;      // 3 (8) input channels -> 64: wants the image of dvd_conv_thin_image in `wq` instead
-    if (dvd_conv_thin_out_ok(d)) return 3;     // 64 -> 3 (8) channels: dvd_conv_thin_out_image
-    return ((pl.halo || pl.smallf) && d->dtype == DVD_BF16) ? 1 : 0;
-}
-
-extern "C" int dvd_pack_conv_weight(int dtype, const float* w, const float* sigma, int Cout, int Cin, int ntaps,
-                                    int Cip, int co_off, int co_tot_f, int co_tot_d, void* wf, void* wd,
-                                    int kt, int kh, int kw, int ci_off, int ci_tot, void* stream) {
-    if (!w || (!wf && !wd) || Cout <= 0 || Cin <= 0 || ntaps != kt * kh * kw) return DVD_E_ARG;
-    if (ci_tot <= 0) { ci_off = 0; ci_tot = Cin; }
-    if (ci_off < 0 || ci_off + Cin > ci_tot) return DVD_E_ARG;
-    if ((Cip & 7) || Cip < Cin || (wd && (co_tot_d & 7))) return DVD_E_SHAPE;
-    PackK p{w, sigma, (char*)wf, (char*)wd, Cout, Cin, ntaps, Cip, co_off, co_tot_f, co_tot_d, kt, kh, kw, ci_off, ci_tot};
-    const long long n = (long long)Cout * Cip * ntaps;
-    if (dtype == DVD_BF16) pack_weight_kernel<bf16_t><<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(p);
-    else if (dtype == DVD_F32) pack_weight_kernel<float><<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(p);
-    else return DVD_E_ARG;
-    return launch_status();
-}
-
-extern "C" int dvd_pack_conv_weight_batched(int dtype, const dvd_pack_item* items, int n, void* stream) {
-    if (!items || n <= 0) return DVD_E_ARG;
-    if (dtype != DVD_BF16 && dtype != DVD_F32) return DVD_E_ARG;
-    for (int i = 0; i < n; ++i) {           // validate everything before the first launch
-        const dvd_pack_item& t = items[i];
-        if (!t.w || (!t.wf && !t.wd) || t.Cout <= 0 || t.Cin <= 0 || t.ntaps != t.kt * t.kh * t.kw) return DVD_E_ARG;
-        const int ci_off = t.ci_tot <= 0 ? 0 : t.ci_off, ci_tot = t.ci_tot <= 0 ? t.Cin : t.ci_tot;
-        if (ci_off < 0 || ci_off + t.Cin > ci_tot) return DVD_E_ARG;
-        if ((t.Cip & 7) || t.Cip < t.Cin || (t.wd && (t.co_tot_d & 7))) return DVD_E_SHAPE;
-    }
-    for (int i0 = 0; i0 < n; i0 += kPackBatch) {
-        PackBatchK b;
-        b.n = n - i0 < kPackBatch ? n - i0 : kPackBatch;
-        long long blocks = 0;
-        for (int j = 0; j < b.n; ++j) {
-            const dvd_pack_item& t = items[i0 + j];
-            const int ci_off = t.ci_tot <= 0 ? 0 : t.ci_off, ci_tot = t.ci_tot <= 0 ? t.Cin : t.ci_tot;
-            b.it[j] = PackK{t.w, t.sigma, (char*)t.wf, (char*)t.wd, t.Cout, t.Cin, t.ntaps, t.Cip, t.co_off, t.co_tot_f, t.co_tot_d,
-                            t.kt, t.kh, t.kw, ci_off, ci_tot};
-            b.first[j] = (int)blocks;
-            blocks += cdiv((long long)t.Cout * t.Cip * t.ntaps, 256);
-        }
-        if (blocks >= (1ll << 31)) return DVD_E_SHAPE;
-        b.first[b.n] = (int)blocks;
-        if (dtype == DVD_BF16) pack_weight_batched_kernel<bf16_t><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(b);
-        else pack_weight_batched_kernel<float><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(b);
-    }
     return launch_status();
 }

@@ -14,7 +14,7 @@
 // kernels below reduce the fp32 slabs while applying the non-linearities.
 // Backward walks t = T-1..0 with two backward-data convs per step; every weight gradient and the
 // x-path gradient are batched over all T by the caller afterwards (dg holds d(pre-activation)).
-#include "common.h"
+#include "conv_common.h"
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -461,12 +461,6 @@ int stack_kind(const dvd_gru_stack_desc* s) {
     for (int l = 0; l < s->n_layers; ++l) t256 += (long long)cdiv(a.B, 4) * cdiv(2 * s->layer[l].hidden, 128);
     return t256 >= 256 ? 2 : 3;
 }
-long long kind_mtiles(int kind, int B, int H, int W) {
-    const long long M = (long long)B * H * W;
-    return kind == 0 ? cdiv(M, 256) : kind == 1 ? cdiv(M, 128) : cdiv(B, kind == 2 ? 4 : kind == 3 ? 2 : 8);
-}
-long long kind_tile_floats(int kind) { return (kind == 0 || kind == 2) ? 32768 : 16384; }     // accumulators of one output tile
-
 int stack_check(const dvd_gru_stack_desc* s, bool backward) {
     if (!s || s->n_layers < 1 || s->n_layers > DVD_GRU_STACK_MAX) return DVD_E_ARG;
     const dvd_gru_desc& a = s->layer[0];
@@ -496,7 +490,7 @@ void member_conv(Member& m, const dvd_gru_desc& L, const void* in, int C, int ld
     dvd_conv_desc& d = m.d;
     d.dtype = L.dtype; d.frames = L.B; d.T = 1; d.H = L.H; d.W = L.W; d.C = C; d.ldi = ldi; d.Cout = Cout; d.ldo = Cout;
     d.kt = 1; d.kh = L.k; d.kw = L.k; d.nsplit = 1; d.in = in; d.w = w; d.wq = wq; d.wq_kind = 1;
-    m.tiles = kind_mtiles(kind, L.B, L.H, L.W) * cdiv(Cout, 128);
+    m.tiles = (long long)cdiv((long long)L.B * L.H * L.W, kGroupKind[kind].rows) * cdiv(Cout, 128);
     m.kchunks = (C + 31) / 32;
 }
 
@@ -542,11 +536,11 @@ SplitPlan plan_splits(int kind, bool backward, int n, const Member* m, long long
     std::lock_guard<std::mutex> lock(mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
-    const int slots = (kind == 0 || kind == 2) ? 64 : 96;
+    const int slots = kGroupKind[kind].slots;
     // fitted on tools/gru_microbench.py stack (B = 64; K steps of the launch's tile shape): a split tile is cheap on 4 x 4 frames
     // (64 KB slabs, few tiles) and dear on 256-row tiles (128 KB slabs; the tile's last workgroup combines, then runs the epilogue):
     // 8 x 8 forward 13.85 -> 12.87 ms with only the 5 x 5 layer split, 4 x 4 5.39 / 6.09 -> 5.03 / 5.56, 16 x 16 backward 46.1 -> 45.0
-    double fixed = (kind == 0 || kind == 2) ? 12.0 : 16.0;
+    double fixed = kGroupKind[kind].rows == 256 ? 12.0 : 16.0;
     double split_cost = kind == 4 ? 3.0 : kind == 0 ? 150.0 : backward ? 50.0 : 80.0;
 #ifdef DVD_STACK_SEARCH_DEBUG
     if (const char* e = getenv("DVD_SS_FIXED")) fixed = atof(e);
@@ -609,7 +603,7 @@ int run_group(const dvd_gru_stack_desc* s, int kind, Member* m, GruEpi* g, int n
     // measured (tools/gru_microbench.py stack, B = 64): (target, cap) = (768, 4) 5.46 / 6.99 ms forward / backward on 4 x 4 frames,
     // (768, 8) 5.66 / 6.16; 8 x 8 frames: (768, 4) 14.86 / 15.09, (768, 8) 14.93 / 15.95, (384, 4) 14.46 / 16.53, (1536, *) slower
     const long long cap = (kind == 4 && backward) ? 8 : 4;
-    const long long target = (kind == 0 || kind == 2) ? 512 : 768;
+    const long long target = 8 * kGroupKind[kind].slots;            // the measured 512 : 768 (that they equal the slots of eight XCDs is how the table states them, not a derivation)
     long long want = (target + total - 1) / total;
     if (want > cap) want = cap;
     SplitPlan plan{};
@@ -632,7 +626,7 @@ int run_group(const dvd_gru_stack_desc* s, int kind, Member* m, GruEpi* g, int n
         if (ns > 1) {
             if (g[i].mode == 0) g[i].mode = 6;            // direct epilogue behind the in-launch combine
             g[i].slabs = s->ws + cursor; g[i].tickets = s->layer[0].tickets;
-            cursor += ns * m[i].tiles * kind_tile_floats(kind);
+            cursor += ns * m[i].tiles * kGroupKind[kind].tile_floats;      // accumulators of one output tile
         }
         d[i] = m[i].d;
     }

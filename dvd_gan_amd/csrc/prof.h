@@ -4,6 +4,15 @@
 #include <vector>
 #include <mutex>
 
+// ProfRec::variant of a forward / backward-data launch (kind 0) = its slot in dvd_prof_report_variants (0: every launch); bench.py,
+// tools/ and the tests read the numbers.  HALO: halo-staged kernels, weights through LDS or from L2; TAP: tap-by-tap kernel; FRAME:
+// whole 4 x 4 / 8 x 8 frames on 256- / 128-row tiles; THIN: conv_thin.hip; GROUP: grouped launches of the HALO / FRAME kernels.
+enum ConvVariant {
+    CV_VAR_ALL = 0, CV_VAR_HALO_256x128 = 1, CV_VAR_HALO_128x128 = 2, CV_VAR_HALO_256x64 = 3, CV_VAR_TAP_128x128 = 4,
+    CV_VAR_TAP_256x128 = 5, CV_VAR_TAP_256x256 = 6, CV_VAR_FRAME_256 = 7, CV_VAR_FRAME_128 = 8, CV_VAR_THIN = 9,
+    CV_VAR_GROUP_HALO = 10, CV_VAR_GROUP_FRAME = 11,
+};
+
 namespace dvdprof {
 struct ProfRec { hipEvent_t a, b; double flops; int kind; long long M; int C, Cout, taps, split, flags, variant; };
 extern bool g_prof;

@@ -105,7 +105,6 @@ PACK_BATCH = os.environ.get("DVD_PACK_BATCH", "1") != "0"
 # timing-only experiment (WRONG results): 1 = BN statistics from 4096 rows, 2 = CBN backward sums from two frames -- what folding
 # those two passes into the neighbouring convolutions' epilogues could return at most (profiles/HISTORY.md, round 6)
 EXP_CBN = int(os.environ.get("DVD_EXP_CBN", "0"))
-EXP_SKIP = int(os.environ.get("DVD_EXP_SKIP", "0"))      # 1 = skip the 1 x 1 convolutions on >= 128 k rows (garbage results)
 
 
 class PackBatch:
@@ -271,8 +270,6 @@ def conv_forward(x, wpack, ksize, cout, *, bias=None, res=None, mask=None, act=L
         alloc = torch.zeros if cp_out != cout else torch.empty
         out = alloc(shape, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
     d.out, d.ldo = out.data_ptr(), out.shape[-1]
-    if EXP_SKIP & 1 and k == (1, 1, 1) and M >= (1 << 17):       # timing experiment: the large 1 x 1 convolutions are not launched
-        return out
     L.check(L.lib().dvd_conv_forward(C.byref(d), L.stream()))
     return out
 

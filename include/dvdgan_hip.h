@@ -116,7 +116,8 @@ typedef struct {
 } dvd_conv_desc;
 int dvd_conv_forward(const dvd_conv_desc* d, void* stream);
 /* 1 when dvd_conv_forward serves `d` with d->pool2 set (square 3 / 5 taps, power-of-two frames >= 16 pixels, one K slice,
- * no residual / activation / ConvGRU epilogue), else 0 (the caller runs the plain request and dvd_pool). */
+ * no residual / activation / ConvGRU epilogue), else 0 (the caller runs the plain request and dvd_pool).  A geometry query: the
+ * buffer pointers of `d` (in, w, out) are not looked at, `ws` only as "set or not". */
 int dvd_conv_pool2_ok(const dvd_conv_desc* d);
 /* Fragment-major weight image: [tap][32-channel chunk][32-column block, padded to whole 128-column tiles][k-half pair][lane]
  * [8 channels] -- 1 KiB per MFMA B fragment, fetched by one coalesced 16-byte load per lane.  `w`: a forward or backward-data
@@ -126,7 +127,8 @@ int dvd_conv_fragment_major(int dtype, const void* w, void* wq, int ntaps, int C
 /* n images in one launch per 32 items (ABI 13; `items`: HOST array, copied into the kernel arguments): the packs of a whole ConvGRU. */
 typedef struct { const void* w; void* wq; int ntaps, Cout, C; } dvd_frag_item;
 int dvd_conv_fragment_major_batched(int dtype, const dvd_frag_item* items, int n, void* stream);
-int dvd_conv_wants_fragment_major(const dvd_conv_desc* d);     /* 0 = no, 1 = fragment-major image, 2 / 3 = the thin-input / thin-output image below */
+int dvd_conv_wants_fragment_major(const dvd_conv_desc* d);     /* 0 = no (also d == NULL), 1 = fragment-major image, 2 / 3 = the thin-input / thin-output image below;
+                                                                  a geometry query as dvd_conv_pool2_ok: in / w / out / wq / wq_kind are not looked at */
 /* 3 x 3 (x 3) convolutions from 3 (padded to 8) input channels to 64 output channels (the discriminator stems, the backward-data
  * pass of the RGB layer) fold their KW taps into the K dimension; they take, in `wq`, this image of their [kt*9][64][8] pack:
  * [tap row][k half][channel block][lane][8] (ABI 10). */

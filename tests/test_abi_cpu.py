@@ -187,6 +187,84 @@ def test_pool2_requests_skip_the_thin_kernels(cin, cout, kind, hw):
     assert lib.dvd_conv_wants_fragment_major(ctypes.byref(d)) == 1
 
 
+CONV_QUERY_PINS = [    # per case of test_gpu_conv.CASES: "forward backward-data", each (nsplit 1, 2) x (pool2 0, 1) -> wants digit, pool2_ok digit
+    "10000000 10000000", "10001000 10001000", "00000000 00000000", "10000000 10111000", "10110000 10110000", "10110000 10110000",
+    "00000000 00000000", "00000000 00000000", "10001000 10001000", "10110000 10111000", "00000000 00000000", "10111000 10111000",
+    "10000000 10111000", "10110000 10110000", "10001000 10001000", "10110000 10111000", "10000000 10111000", "10110000 10111000",
+    "10111000 10111000", "10111000 10111000", "10111000 10111000", "10111000 10111000", "10001000 10001000", "00000000 00000000",
+    "10001000 10001000", "10110000 10111000", "10111000 10111000", "10111000 10111000", "10001000 10001000", "10111000 10111000",
+    "10111000 10111000", "10001000 10001000", "10001000 10111000", "10001000 10111000", "10001000 10111000", "10001000 10111000",
+    "10001000 10111000", "10001000 10001000", "10111000 10111000", "10110000 10111000", "00000000 00000000", "10001000 10001000",
+    "10000000 10000000", "10000000 10001000", "10000000 10001000", "10001000 10001000", "10001000 10001000", "20110000 30111000",
+    "10001000 10001000", "30111000 20110000", "10001000 20001000", "00000000 00000000", "00000000 00000000", "00000000 00000000",
+    "00000000 00000000", "00000000 00000000", "00000000 00000000", "10001000 20110000", "10000000 30111000",
+]
+
+
+def test_conv_queries_are_pinned():
+    """dvd_conv_wants_fragment_major / dvd_conv_pool2_ok over the forward and the backward-data geometry of every case of
+    tests/test_gpu_conv.py::CASES (bf16) x nsplit {1, 2} x pool2 {0, 1}: both read the forward planner's plan (cv_plan, made
+    "geometry only"), so a change of a family rule shows here without a GPU.  The values were generated on the CPU from the library
+    of the commit before the planner was split into steps, with this loop.  Queries only, nothing is launched.
+    (The refusals of dvd_conv_forward_group: test_group_refusals_are_pinned.)"""
+    from dvd_gan_amd import lib as L
+    from test_gpu_conv import CASES
+    lib = L.lib()
+    pad8 = lambda c: (c + 7) // 8 * 8
+    assert len(CONV_QUERY_PINS) == len(CASES)
+    bad = []
+    for case, want in zip(CASES, CONV_QUERY_PINS):
+        F_, Cin, Cout, sp, ks, up2, relu = case
+        H, W = (v * (2 if up2 else 1) for v in sp[-2:])
+        got = []
+        for cin, cout, u, r in ((pad8(Cin), Cout, up2, relu), (pad8(Cout), pad8(Cin), False, False)):
+            s = ""
+            for ns in (1, 2):
+                for p2 in (0, 1):
+                    d = L.ConvDesc()
+                    d.dtype, d.frames, d.T, d.H, d.W = L.BF16, F_, sp[0] if len(sp) == 3 else 1, H, W
+                    d.C, d.ldi, d.Cout, d.ldo = cin, cin, cout, pad8(cout)
+                    d.kt, d.kh, d.kw = ks if len(ks) == 3 else (1,) + tuple(ks)
+                    d.up2, d.relu_in, d.nsplit, d.pool2 = int(u), int(r), ns, p2
+                    d.inp = d.w = d.out = 1               # never dereferenced by the queries
+                    if ns > 1:
+                        d.ws = 1                          # (split-K writes slabs)
+                    s += "%d%d" % (lib.dvd_conv_wants_fragment_major(ctypes.byref(d)), lib.dvd_conv_pool2_ok(ctypes.byref(d)))
+            got.append(s)
+        if " ".join(got) != want:
+            bad.append((case, " ".join(got), want))
+    assert not bad, bad
+
+
+GROUP_REFUSALS = dict(
+    [("n=0", -1), ("n=7", -1), ("kind=-1", -1), ("kind=5", -1)]
+    + [("side=%d,kind=%d" % (s, k), -2) for s, fits in ((16, (0, 1)), (8, (2, 3)), (4, (4,))) for k in range(5) if k not in fits]
+    + [("side=%d,%s" % (s, f), -1) for s in (16, 8, 4) for f in ("relu_in", "up2", "ws")])
+
+
+def test_group_refusals_are_pinned(tmp_path):
+    """The refusals of dvd_conv_forward_group that return before any launch, with their codes (DVD_E_ARG = -1, DVD_E_SHAPE = -2): n
+    and kind out of range, a member whose geometry does not fit `kind` (every frame side under every kind of kGroupKind it does not
+    belong to), a member with relu_in, up2 or ws.  The entry point is hidden from the shared library's exports, so
+    tests/native/group_refusals.cpp is linked against the object files build.sh left (static linking ignores visibility) and run: no
+    GPU is touched.  The codes are those of the same program linked against the objects of the commit before the group kinds became
+    a table."""
+    import glob
+    import shutil
+    import subprocess
+    csrc = os.path.join(ROOT, "dvd_gan_amd", "csrc")
+    objs = sorted(glob.glob(os.path.join(csrc, "build", "*.o")))
+    if not objs or not shutil.which("hipcc"):
+        pytest.skip("no build/*.o or no hipcc: the library was not built by csrc/build.sh in this tree")
+    main_o, prog = str(tmp_path / "main.o"), str(tmp_path / "group_refusals")
+    subprocess.check_call(["hipcc", "-x", "hip", "--cuda-host-only", "-std=c++17", "-I", csrc, "-c",
+                           os.path.join(ROOT, "tests", "native", "group_refusals.cpp"), "-o", main_o])
+    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-o", prog, main_o] + objs)
+    out = subprocess.check_output([prog]).decode()
+    got = {l.split()[0]: int(l.split()[1]) for l in out.splitlines()}
+    assert got == GROUP_REFUSALS
+
+
 def test_attention_refusal_rules_need_no_gpu():
     """The shapes the attention entry points refuse before any launch (DVD_E_SHAPE): the MFMA kernels past 4096 tokens, the
     separable cell past an attended size of 64, the fp32 kernels' LDS limits -- forward [QB][Nk] scores + queries + partial

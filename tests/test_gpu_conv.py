@@ -337,6 +337,69 @@ def test_f32_to_bf16_is_round_to_nearest_even():
     assert torch.equal(got.view(torch.int16)[~nan], want.view(torch.int16)[~nan])
 
 
+def conv_variants(case, dtype):
+    """The kernel variants (dvd_prof_report_variants, kind 0; ConvVariant in csrc/prof.h) of the forward and the backward-data call
+    test_conv_forward_dgrad_wgrad makes for `case` -> "plain/with image": without a weight image, and (bf16) once more with the image
+    the library's query asks for (kern.conv_forward builds it where dvd_conv_wants_fragment_major says so)."""
+    import ctypes as C
+    from dvd_gan_amd import kern as K, lib as L
+    F_, Cin, Cout, sp, ks, up2, relu_in = case
+    g = torch.Generator().manual_seed(hash(case) & 0xffff)
+    x = torch.randn(F_, Cin, *sp, generator=g)
+    w = torch.randn(Cout, Cin, *ks, generator=g) / (Cin * ks[-1] * ks[-2]) ** 0.5
+    b = torch.randn(Cout, generator=g)
+    osp = tuple(sp[:-2]) + tuple(v * (2 if up2 else 1) for v in sp[-2:])
+    gy = torch.randn(F_, Cout, *osp, generator=g)
+    xc, gyc = K.to_cl(x.to("cuda"), dtype), K.to_cl(gy.to("cuda"), dtype)
+    pk = K.PackedConv(dtype, Cout, Cin, ks, "cuda").fill(w.to("cuda"))
+    lib, seen = L.lib(), []
+    lib.dvd_prof_report_variants.restype = C.c_longlong
+    for image in ((False, True) if dtype == torch.bfloat16 else (False,)):
+        wf = dict(wq=lambda: pk.fragment_major("wf")) if image else {}
+        wd = dict(wq=lambda: pk.fragment_major("wd")) if image else {}
+        lib.dvd_prof_enable(1)
+        try:
+            K.conv_forward(xc, pk.wf, ks, Cout, bias=b.to("cuda"), up2=up2, relu_in=relu_in, out_f32=True, **wf)
+            K.conv_forward(gyc, pk.wd, ks, pk.cip, out_f32=True, **wd)
+            torch.cuda.synchronize()
+        finally:
+            lib.dvd_prof_enable(0)
+        n = (C.c_longlong * 12)()
+        lib.dvd_prof_report_variants(0, 12, n, None, None)            # drains the records (tests/test_gpu_gru.py::_drain)
+        seen.append(",".join(str(v) for v in range(1, 12) if n[v] > 0))
+    return "/".join(seen)
+
+
+# conv_variants of every case, in the order of CASES: produced by this helper with the library of the commit before the forward
+# planner was split into steps (DVD_LIB_PATH); the planner must keep choosing the same kernels.
+CONV_VARIANTS = {
+    torch.float32: [
+        "4", "4", "4", "2", "2", "2", "4", "4", "4", "1,2",
+        "4", "2", "2", "2", "2", "1", "1", "1", "1,2", "2",
+        "2", "2", "4", "4", "2", "2", "2", "2", "4", "2",
+        "2", "2", "2", "2", "2", "2", "2", "4", "2", "2",
+        "4", "4", "4", "4", "4", "4", "4", "2", "2", "2",
+        "2", "4", "4", "4", "4", "4", "4", "2", "2",
+    ],
+    torch.bfloat16: [
+        "4/8", "4/8", "4/4", "2/2", "2/2", "2/2", "4/4", "4/4", "4/8", "1,2/1,2",
+        "4,6/4,6", "2/2", "2/2", "2/2", "2/2", "3/3", "3/3", "1,3/1,3", "1,2/1,2", "2/2",
+        "2/2", "2/2", "4/8", "4/4", "2/2", "2/2", "2/2", "2/2", "4/8", "2/2",
+        "2/2", "2/2", "2/2", "2/2", "2/2", "2/2", "2/2", "4/8", "2/2", "2/2",
+        "4/4", "4/8", "4/8", "4/8", "4/8", "4/8", "4/8", "2/9", "2/2", "2/9",
+        "2/2,9", "4/4", "4/4", "4/4", "4/4", "4/4", "4/4", "2/2,9", "2/2,9",
+    ],
+}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_conv_kernel_variants_are_pinned(dtype):
+    assert len(CONV_VARIANTS[dtype]) == len(CASES)
+    got = [conv_variants(case, dtype) for case in CASES]
+    bad = [(case, a, b) for case, a, b in zip(CASES, got, CONV_VARIANTS[dtype]) if a != b]
+    assert not bad, bad
+
+
 DEV = "cuda"
 
 

@@ -45,7 +45,7 @@ CASES = {
     5: (2, 16, 16, 24, 5, 3),       # one K chunk: the halo kernel serves it only unsplit
     6: (3, 16, 16, 64, 3, 3),       # halo 128-row tiles, weights from LDS / from L2
     7: (32, 64, 64, 64, 3, 2),      # 512 tiles, unsplit: halo 256-row for u|r, the thin 256 x 64 tile for the out gate and d(hr)
-    8: (1024, 8, 8, 128, 3, 2),     # the 8-wave 256 x 256 tile with a gate epilogue (conv_plan wants t256 >= 256)
+    8: (1024, 8, 8, 128, 3, 2),     # the 8-wave 256 x 256 tile with a gate epilogue (cv_choose_kernel wants t256 >= 256)
     9: (5, 6, 6, 24, 3, 3),         # division indexing
     10: (2, 6, 12, 24, 3, 3),       # division indexing, H != W
     11: (2, 8, 16, 40, 3, 3),       # H != W with shift indexing
@@ -56,7 +56,7 @@ ALL4 = {r: {4} for r in "abcd"}
 # kernel variants (dvd_prof_report_variants, kind 0) a (case, fragment-major images supplied) must show per route:
 # 1 / 2 / 3 = halo 256 x 128 / 128 x 128 / 256 x 64, 4 = tap-by-tap 128-row, 6 = 8-wave 256 x 256, 8 = whole-frame 128-row tiles
 # (4 x 4 frames are always recorded as 8).  The whole-frame and halo kernels take a split only over channel chunks
-# (conv_plan), so under the policy's factors these narrow layers stay on the tap-by-tap kernel and reach them unsplit (route c).
+# (cv_choose_kernel), so under the policy's factors these narrow layers stay on the tap-by-tap kernel and reach them unsplit (route c).
 FAMILY = {(1, False): ALL4, (1, True): {"c": {8}}, (2, False): ALL4, (2, True): {"c": {8}}, (3, False): ALL4, (3, True): {"c": {8}},
           (4, False): ALL4, (4, True): {"c": {8}}, (5, False): {"a": {4}, "c": {2}}, (5, True): {"a": {4}, "c": {2}},
           (6, False): {"c": {2}}, (6, True): {"c": {2}}, (7, False): {r: {1, 3} for r in "abcd"}, (7, True): {r: {1, 3} for r in "abcd"},
