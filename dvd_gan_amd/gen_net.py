@@ -158,6 +158,13 @@ class Generator(nn.Module):
         self.grad_ready_hook = None                 # callable(first finished module index), armed around backward
         self.grad_ready_stages = (2, 5, 8)          # after each [ConvGRU, GResBlock, GResBlock] group but the last
 
+    def ortho_exclude(self):
+        """The matrices orthogonal regularization (config.g_ortho) leaves alone: the shared class embedding (as BigGAN does) and
+        every ConditionalNorm.embed.weight -- the reference's initialisation (sn_layers.py:212-213) sets the first C columns of
+        every row to about 1 and the rest to 0, so its rows are nearly equal by design and the penalty would fight it."""
+        from .sn_layers import ConditionalNorm
+        return [self.embedding.weight] + [m.embed.weight for m in self.modules() if isinstance(m, ConditionalNorm)]
+
     def forward(self, x, class_id, hidden=None, cond=None):
         """hidden (frame-conditional variant, BASELINE configs[4]): initial ConvGRU states supplied by the caller -- one entry
         per ConvGRU of the stack (4), each None or a list of that ConvGRU's per-layer states [B, hidden_l, S, S] fp32 (None

@@ -546,6 +546,31 @@ def adam_ema_step(p, g, m, v, ema, lr, b1, b2, eps, step, decay):
                                       _f(b2), _f(eps), int(step), _f(decay), L.stream()))
 
 
+ORTHO_COLS = 8                                   # DVD_ORTHO_COLS of include/dvdgan_hip.h: off, h, w | planner columns
+ORTHO_OFF, ORTHO_H, ORTHO_W = 0, 1, 2
+
+
+def ortho_prepare(items):
+    """dvd_ortho_prepare on a contiguous CPU int64 table [n][ORTHO_COLS] whose off / h / w columns are filled: fills the planner's
+    columns in place (host only, no device) and returns (tiles of M = penalty slots, workspace floats)."""
+    assert items.dtype == torch.int64 and not items.is_cuda and items.is_contiguous() and items.dim() == 2 \
+        and items.shape[1] == ORTHO_COLS
+    lib = L.lib()
+    ws = C.c_longlong(0)
+    tiles = lib.dvd_ortho_prepare(C.c_void_p(items.data_ptr()), int(items.shape[0]), C.byref(ws))
+    if tiles < 0:
+        L.check(int(tiles))
+    return int(tiles), int(ws.value)
+
+
+def ortho_grad(p, g, items_host, items_dev, strength, ws, penalty=None):
+    """g += 2 * strength * M W for every matrix of the prepared table (views of the flat fp32 buffers p and g at equal offsets),
+    M = W W^T with a zero diagonal, in two launches; `penalty` (a float64 device scalar) receives sum 1/2 ||M||_F^2."""
+    assert p.dtype == g.dtype == torch.float32 and (penalty is None or penalty.dtype == torch.float64)
+    L.check(L.lib().dvd_ortho_grad(L.ptr(p), L.ptr(g), C.c_void_p(items_host.data_ptr()), L.ptr(items_dev),
+                                   int(items_host.shape[0]), _f(strength), L.ptr(ws), L.ptr(penalty), L.stream()))
+
+
 def ema_step(ema, p, decay):
     L.check(L.lib().dvd_ema_step(L.ptr(ema), L.ptr(p), _ll(p.numel()), _f(decay), L.stream()))
 

@@ -15,6 +15,9 @@ Beyond the reference: config.ema_decay > 0 keeps an exponential moving average o
 generator's Adam launch (optim.FlatAdam); `ema_weights()` / `sample(use_ema=True)` / `predict(use_ema=True)` compute with it and
 `save_models` writes it as `{step}_G_ema.pth`.  A frame-conditional Trainer also has `rollout()` (autoregressive prediction past
 n_frames) and `evaluate_prediction()` (PSNR / SSIM curves over the horizon, mean and best of N sampled futures; metrics.py).
+config.g_ortho = beta > 0 adds BigGAN's orthogonal regularizer (Brock et al. 2019, eq. 3) to the generator's gradient right before
+its Adam launch (optim.FlatAdam(ortho=beta)): every trainable matrix of G except the class embedding and the conditional-norm
+embeddings; `ortho_penalty` is the device scalar sum 1/2 ||offdiag(W W^T)||_F^2 of the last generator step.
 Out of scope: tensorboard logging, sample grids, dataset loaders.
 """
 import contextlib
@@ -129,6 +132,10 @@ class Trainer(object):
         if not 0.0 <= self.ema_decay < 1.0 or self.ema_start < 0 or self.ema_standing_stats < 0:
             raise ValueError(f"ema_decay={self.ema_decay} (in [0, 1)), ema_start={self.ema_start}, "
                              f"ema_standing_stats={self.ema_standing_stats} (both >= 0)")
+        # orthogonal regularization of the generator's matrices (0 = off): strength beta of g += beta * 2 M W
+        self.g_ortho = float(getattr(c, "g_ortho", 0.0))
+        if not 0.0 <= self.g_ortho < float("inf"):
+            raise ValueError(f"g_ortho={self.g_ortho} must be a finite strength >= 0")
         self.lr_decay = getattr(c, "lr_decay", 0.9999)
         self.pretrained_model = getattr(c, "pretrained_model", None)
         self.model_save_path = os.path.join(getattr(c, "model_save_path", "./models"), getattr(c, "version", ""))
@@ -189,6 +196,12 @@ class Trainer(object):
                     m.replicas = (self.exchange.world, D.all_reduce_sum_)
         self.select_opt_schr()
 
+    @property
+    def ortho_penalty(self):
+        """Device scalar (float64): sum over the regularised matrices of 1/2 ||offdiag(W W^T)||_F^2, on the weights the last
+        generator step started from, unscaled; None when config.g_ortho = 0 or before the first step."""
+        return self.g_optimizer.ortho_penalty
+
     def _sync_replicas(self):
         D.broadcast_state((self.G, self.D_s, self.D_t),
                           (self.g_optimizer.flat, self.ds_optimizer.flat, self.dt_optimizer.flat))
@@ -196,7 +209,8 @@ class Trainer(object):
     # ---- trainer.py:134-176
     def select_opt_schr(self):
         betas = (self.beta1, self.beta2)
-        self.g_optimizer = FlatAdam(self.G.parameters(), self.g_lr, betas, ema_decay=self.ema_decay, ema_start=self.ema_start)
+        self.g_optimizer = FlatAdam(self.G.parameters(), self.g_lr, betas, ema_decay=self.ema_decay, ema_start=self.ema_start,
+                                    ortho=self.g_ortho, ortho_exclude=self.G.ortho_exclude() if self.g_ortho else ())
         # (the optional attention blocks and the conditioning encoder sit at the END of the parameter order but finish their
         #  gradients late in the backward pass -- the encoder's last of all, behind the dh0 of the first ConvGRU: with them the
         #  generator's gradient goes in one piece)

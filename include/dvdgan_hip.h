@@ -440,6 +440,36 @@ int dvd_frame_metrics(const float* pred, long long p_sb, long long p_st, long lo
                       long long t_sb, long long t_st, long long t_sc, long long B, int T, int C, int H, int W, int flags,
                       float* mse, float* ssim, void* ws, void* stream);
 
+/* Orthogonal regularization of weights (no reference counterpart; Brock et al. 2019, eq. 3; optim.FlatAdam(ortho = beta).step;
+ * additions: the ABI version stays 13).  For every item i, a row-major fp32 matrix W_i = p + off_i viewed as [h_i][w_i]:
+ *   M_i = W_i W_i^T with its diagonal set to exact zeros,  R(W_i) = 1/2 ||M_i||_F^2,  dR/dW_i = 2 M_i W_i,
+ *   g[off_i ...] = fl(g + fl(s * (M_i W_i)))  with s = 2 * strength formed on the host: two roundings, never a fused multiply-add.
+ * Both products run on v_mfma_f32_32x32x2_f32 (exact fp32).  The whole table takes two launches (all M_i, then all updates) and,
+ * with `penalty` != NULL, a third that leaves *penalty = sum_i R(W_i), unscaled: fp32 elements of M squared and summed in fp64,
+ * one slot per tile, the slots added in a fixed order.  No atomics: what an item receives depends on nothing else in the table,
+ * and reruns are bit-equal.  Any h >= 1, w >= 1, any 4-byte aligned offsets; an item with h = 1 has an empty M and is skipped.
+ * The table is `long long items[n][DVD_ORTHO_COLS]`: the caller fills DVD_ORTHO_OFF / _H / _W (offset in floats, the same in p and
+ * g), dvd_ortho_prepare -- host only, no device needed -- fills the planner's columns (workspace offset of M_i, first block of the
+ * item in either launch, and the launch order of the items: deepest products first), stores the workspace size in *ws_floats
+ * (floats; the workspace must be 8-byte aligned) and returns the number of M tiles (>= 0) or DVD_E_ARG (null pointer, n < 1,
+ * h < 1, w < 1, negative offset) / DVD_E_SHAPE (h > DVD_ORTHO_MAX_H, more than 2^31 - 1 blocks or 2^40 elements).
+ * dvd_ortho_grad takes the prepared table twice, in host memory (checked against the planner before any launch: DVD_E_ARG when
+ * it is not what dvd_ortho_prepare leaves) and in device memory (uploaded once by the caller).  strength must be finite and
+ * >= 0.  p, g and ws must not overlap (not checked). */
+#define DVD_ORTHO_COLS 8
+#define DVD_ORTHO_OFF 0
+#define DVD_ORTHO_H 1
+#define DVD_ORTHO_W 2
+#define DVD_ORTHO_WS 3        /* planner: offset of M_i [h][h] in the workspace, floats                          */
+#define DVD_ORTHO_GRAM0 4     /* planner: first block of the item in the Gram launch                             */
+#define DVD_ORTHO_APPLY0 5    /* planner: first block of the item in the apply launch                            */
+#define DVD_ORTHO_GORDER 6    /* planner: row r holds the index of the item at rank r of the Gram launch         */
+#define DVD_ORTHO_AORDER 7    /* planner: the same for the apply launch                                          */
+#define DVD_ORTHO_MAX_H 32768
+long long dvd_ortho_prepare(long long* items, int n, long long* ws_floats);
+int dvd_ortho_grad(const float* p, float* g /* += */, const long long* items_host, const long long* items_dev, int n,
+                   float strength, float* ws, double* penalty /* or NULL */, void* stream);
+
 /* 2-D self attention (Discriminators.py:100-119: bmm, softmax, bmm, gamma*out + x) */
 int dvd_attention_forward(int dtype, const void* qkv, int ldq, int dq, int koff, int voff, const void* x, int ldx, int C,
                           const float* gamma, void* y, void* att_out, float* A, long long frames, int N, void* stream);
