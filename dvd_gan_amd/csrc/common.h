@@ -78,6 +78,24 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ----------------------------------------------------------------------------- Adam / weight average, one element
+// torch.optim.Adam (no weight decay / amsgrad), trainer.py:136-141.  misc.hip (adam_kernel, adam_ema_kernel, ema_kernel) and
+// guard.hip (adam_guard_kernel) share these two functions so that every launch produces the same bits.
+// One element of the update; adam_kernel and adam_ema_kernel share it so both produce the same bits.  Contraction is off:
+// whether a multiply and an add fuse must not depend on the kernel this is inlined into (adam_kernel compiles to separate
+// multiplies and adds, and its results are pinned by tests/test_gpu_ema.py against the fused launch).
+__device__ __forceinline__ float adam_elem(float pi, float gi, float& m, float& v, float lr_over_bc1, float b1, float b2,
+                                           float eps, float bc2_sqrt) {
+#pragma clang fp contract(off)
+    const float mi = m + (gi - m) * (1.f - b1);
+    const float vi = v * b2 + (1.f - b2) * gi * gi;
+    m = mi;
+    v = vi;
+    return pi - lr_over_bc1 * mi / (sqrtf(vi) / bc2_sqrt + eps);
+}
+// ema = d * ema + (1 - d) * p as fmaf(d, ema, omd * p): d = 0 leaves ema == p bit for bit (omd = 1).
+__device__ __forceinline__ float ema_elem(float e, float p, float d, float omd) { return fmaf(d, e, omd * p); }
+
 // value a T-typed store would keep (bf16 rounding; identity for fp32)
 template <typename T> __device__ __forceinline__ float round_to(float v) { return v; }
 template <> __device__ __forceinline__ float round_to<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
@@ -132,3 +150,14 @@ static inline int ilog2_exact(int v) {   // host: log2 of a power of two, -1 oth
 }
 static inline int launch_status() { return hipGetLastError() == hipSuccess ? DVD_OK : DVD_E_LAUNCH; }
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
+
+// Launch shape of the memory-bound streams over flat fp32 buffers (misc.hip: adam_ema_kernel, ema_kernel, swap_kernel; guard.hip:
+// adam_guard_kernel): a capped grid of 256-thread workgroups walks n4 16-byte vectors, then the elements from 4 * n4 on.
+constexpr unsigned FLAT_MAX_BLOCKS = 2048;          // 8 workgroups of 256 threads for each of the MI355X's 256 CUs
+// n4 of the flat kernels: whole 16-byte vectors when every pointer is 16-byte aligned, else 0 (all scalar)
+static inline long long flat_n4(long long n, uintptr_t ptr_bits) { return (ptr_bits & 15) ? 0 : n / 4; }
+static inline unsigned flat_grid(long long n, long long n4) {
+    const long long g = ((n4 ? n4 : n) + 255) / 256;          // capped before the narrowing: no wrap for any n
+    return g < (long long)FLAT_MAX_BLOCKS ? (unsigned)g : FLAT_MAX_BLOCKS;
+}
+static inline bool decay_ok(float d) { return d >= 0.f && d < 1.f; }      // false for NaN as well

@@ -304,18 +304,7 @@ __global__ void adv_loss_kernel(const float* out, long long n, int hinge, int re
 
 // ----------------------------------------------------------------------------- Adam
 // torch.optim.Adam (no weight decay / amsgrad), trainer.py:136-141
-// One element of the update; adam_kernel and adam_ema_kernel share it so both produce the same bits.  Contraction is off:
-// whether a multiply and an add fuse must not depend on the kernel this is inlined into (adam_kernel compiles to separate
-// multiplies and adds, and its results are pinned by tests/test_gpu_ema.py against the fused launch).
-__device__ __forceinline__ float adam_elem(float pi, float gi, float& m, float& v, float lr_over_bc1, float b1, float b2,
-                                           float eps, float bc2_sqrt) {
-#pragma clang fp contract(off)
-    const float mi = m + (gi - m) * (1.f - b1);
-    const float vi = v * b2 + (1.f - b2) * gi * gi;
-    m = mi;
-    v = vi;
-    return pi - lr_over_bc1 * mi / (sqrtf(vi) / bc2_sqrt + eps);
-}
+// adam_elem (common.h): one element of the update, shared with adam_ema_kernel and guard.hip so all produce the same bits
 __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long long n, float lr_over_bc1, float b1,
                             float b2, float eps, float bc2_sqrt) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -328,13 +317,11 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long l
 }
 
 // ----------------------------------------------------------------------------- weight average (EMA)
-// ema = d * ema + (1 - d) * p as fmaf(d, ema, omd * p): d = 0 leaves ema == p bit for bit (omd = 1).
-__device__ __forceinline__ float ema_elem(float e, float p, float d, float omd) { return fmaf(d, e, omd * p); }
+// ema_elem (common.h): ema = d * ema + (1 - d) * p
 
-// The three kernels below are memory-bound streams over flat fp32 buffers: a capped grid (FLAT_MAX_BLOCKS) walks n4 16-byte
-// vectors with a grid-stride loop, then the elements from 4 * n4 on one by one.  The host passes n4 = n / 4 when every pointer is
-// 16-byte aligned and n4 = 0 otherwise (the scalar loop then covers everything).
-constexpr unsigned FLAT_MAX_BLOCKS = 2048;          // 8 workgroups of 256 threads for each of the MI355X's 256 CUs
+// The three kernels below are memory-bound streams over flat fp32 buffers: a capped grid (FLAT_MAX_BLOCKS, common.h) walks n4
+// 16-byte vectors with a grid-stride loop, then the elements from 4 * n4 on one by one.  The host passes n4 = n / 4 when every
+// pointer is 16-byte aligned and n4 = 0 otherwise (the scalar loop then covers everything): flat_n4 / flat_grid of common.h.
 
 // Adam (exactly adam_kernel's arithmetic) and the average of the UPDATED weights in one pass
 __global__ __launch_bounds__(256) void adam_ema_kernel(float* p, const float* g, float* m, float* v, float* ema, long long n,
@@ -527,14 +514,6 @@ extern "C" int dvd_adam_step(float* p, const float* g, float* m, float* v, long 
     adam_kernel<<<cdiv(n, 256), 256, 0, S_>>>(p, g, m, v, n, (float)((double)lr / bc1), beta1, beta2, eps, (float)sqrt(bc2));
     return launch_status();
 }
-
-// n4 of the flat kernels: whole 16-byte vectors when every pointer is 16-byte aligned, else 0 (all scalar)
-static inline long long flat_n4(long long n, uintptr_t ptr_bits) { return (ptr_bits & 15) ? 0 : n / 4; }
-static inline unsigned flat_grid(long long n, long long n4) {
-    const long long g = ((n4 ? n4 : n) + 255) / 256;          // capped before the narrowing: no wrap for any n
-    return g < (long long)FLAT_MAX_BLOCKS ? (unsigned)g : FLAT_MAX_BLOCKS;
-}
-static inline bool decay_ok(float d) { return d >= 0.f && d < 1.f; }      // false for NaN as well
 
 extern "C" int dvd_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr,
                                  float beta1, float beta2, float eps, int step, float decay, void* stream) {

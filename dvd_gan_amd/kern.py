@@ -546,6 +546,49 @@ def adam_ema_step(p, g, m, v, ema, lr, b1, b2, eps, step, decay):
                                       _f(b2), _f(eps), int(step), _f(decay), L.stream()))
 
 
+GUARD_CH = 16384                                 # DVD_GUARD_CH of include/dvdgan_hip.h: elements per workgroup of the norm pass
+GUARD_STATE = 8                                  # DVD_GUARD_STATE: doubles of the state block
+GUARD_NORM, GUARD_COEF, GUARD_BAD, GUARD_SKIP, GUARD_SEEN, GUARD_SKIPPED, GUARD_CLIPPED = range(7)
+
+
+def GUARD_CHAIN(n):
+    """The longest chain of fp64 additions between an element of an n-element gradient and the sum of squares dvd_grad_guard takes
+    the root of (csrc/guard.hip), every addition counted, the first one into an accumulator's zero (which is exact) included:
+    16 rounds of a thread's accumulator (GUARD_CH / (256 threads * 4 accumulators)), 2 to join the four accumulators, 6 xor
+    shuffles, 3 to add the four waves; then in the finalizing workgroup ceil(workgroups / 1024) partials per thread, 6 shuffles
+    and 15 to add the sixteen waves.  All terms are >= 0, so |S - exact| <= GUARD_CHAIN(n) * 2^-53 * exact to first order; the
+    exact first addition leaves room for the second-order terms and for the rounding of a correctly rounded reference sum."""
+    nwg = -(-int(n) // GUARD_CH)
+    return GUARD_CH // 1024 + 2 + 6 + 3 + -(-nwg // 1024) + 6 + 15
+
+
+def grad_guard_ws_bytes(n):
+    return int(L.lib().dvd_grad_guard_ws_bytes(_ll(n)))
+
+
+def grad_guard_ws_views(ws, n):
+    """-> (partial float64[W], S float64[1], bad int32[W]): views of a dvd_grad_guard workspace for an n-element gradient."""
+    nwg = -(-int(n) // GUARD_CH)
+    d = ws[:(nwg + 1) * 8].view(torch.float64)
+    return d[:nwg], d[nwg:], ws[(nwg + 1) * 8:(nwg + 1) * 8 + nwg * 4].view(torch.int32)
+
+
+def grad_guard(g, max_norm, skip_nonfinite, step, ws, state, ring=None):
+    """dvd_grad_guard: the fp64 norm of the finite part of the flat fp32 gradient g, the clipping coefficient for `max_norm`
+    (float("inf") = measure only) and the skip decision into `state` (float64[GUARD_STATE], zeroed before its first use); `ring`
+    (float64[R][4], optional) receives row (step - 1) % R = step, norm, coef, bad.  Two launches, no host sync."""
+    assert g.dtype == torch.float32 and state.dtype == torch.float64 and state.numel() == GUARD_STATE
+    assert ring is None or (ring.dtype == torch.float64 and ring.dim() == 2 and ring.shape[1] == 4)
+    L.check(L.lib().dvd_grad_guard(L.ptr(g), _ll(g.numel()), _f(max_norm), int(bool(skip_nonfinite)), _ll(step), L.ptr(ws),
+                                   L.ptr(state), L.ptr(ring), 0 if ring is None else int(ring.shape[0]), L.stream()))
+
+
+def adam_guard_step(p, g, m, v, ema, lr, b1, b2, eps, step, decay, state):
+    """adam_ema_step (ema a tensor) or adam_step (ema None) on g * coef32 of `state`; on a skipped step nothing is written."""
+    L.check(L.lib().dvd_adam_guard_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), _ll(p.numel()), _f(lr), _f(b1),
+                                        _f(b2), _f(eps), int(step), _f(decay), L.ptr(state), L.stream()))
+
+
 ORTHO_COLS = 8                                   # DVD_ORTHO_COLS of include/dvdgan_hip.h: off, h, w | planner columns
 ORTHO_OFF, ORTHO_H, ORTHO_W = 0, 1, 2
 

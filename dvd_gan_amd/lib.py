@@ -52,6 +52,7 @@ def lib():
         _lib.dvd_cbn_backward_ws_floats.restype = C.c_longlong
         _lib.dvd_frame_metrics_ws_bytes.restype = C.c_longlong
         _lib.dvd_ortho_prepare.restype = C.c_longlong
+        _lib.dvd_grad_guard_ws_bytes.restype = C.c_longlong
         if _lib.dvd_abi_version() != ABI_VERSION:
             raise RuntimeError("libdvdgan_hip.so ABI version mismatch: rebuild it")
         # layout handshake: every descriptor mirror below must have the size the library was compiled with

@@ -18,6 +18,10 @@ n_frames) and `evaluate_prediction()` (PSNR / SSIM curves over the horizon, mean
 config.g_ortho = beta > 0 adds BigGAN's orthogonal regularizer (Brock et al. 2019, eq. 3) to the generator's gradient right before
 its Adam launch (optim.FlatAdam(ortho=beta)): every trainable matrix of G except the class embedding and the conditional-norm
 embeddings; `ortho_penalty` is the device scalar sum 1/2 ||offdiag(W W^T)||_F^2 of the last generator step.
+config.g_clip_norm / d_clip_norm > 0 clip the gradient of G / of D_s and D_t (each network on its own) to that norm,
+config.skip_nonfinite leaves a network's weights and Adam state untouched in a step whose gradient holds an inf or a NaN,
+config.grad_log = R keeps the last R steps' norms -- all on the device (optim.FlatAdam's guard): `grad_norms` are device scalars,
+`guard_report()` is the one call that reads them back.
 Out of scope: tensorboard logging, sample grids, dataset loaders.
 """
 import contextlib
@@ -136,6 +140,15 @@ class Trainer(object):
         self.g_ortho = float(getattr(c, "g_ortho", 0.0))
         if not 0.0 <= self.g_ortho < float("inf"):
             raise ValueError(f"g_ortho={self.g_ortho} must be a finite strength >= 0")
+        # gradient guard (all 0 / False = off): clipping norms of G and of the two discriminators, skipping of non-finite steps,
+        # rows of the per-network norm log
+        self.g_clip_norm = float(getattr(c, "g_clip_norm", 0.0))
+        self.d_clip_norm = float(getattr(c, "d_clip_norm", 0.0))
+        self.skip_nonfinite = bool(getattr(c, "skip_nonfinite", False))
+        self.grad_log = int(getattr(c, "grad_log", 0))
+        if not (0.0 <= self.g_clip_norm < float("inf") and 0.0 <= self.d_clip_norm < float("inf")) or self.grad_log < 0:
+            raise ValueError(f"g_clip_norm={self.g_clip_norm}, d_clip_norm={self.d_clip_norm} (finite norms >= 0), "
+                             f"grad_log={self.grad_log} (rows >= 0)")
         self.lr_decay = getattr(c, "lr_decay", 0.9999)
         self.pretrained_model = getattr(c, "pretrained_model", None)
         self.model_save_path = os.path.join(getattr(c, "model_save_path", "./models"), getattr(c, "version", ""))
@@ -202,6 +215,26 @@ class Trainer(object):
         generator step started from, unscaled; None when config.g_ortho = 0 or before the first step."""
         return self.g_optimizer.ortho_penalty
 
+    def _optimizers(self):
+        return (("G", self.g_optimizer), ("Ds", self.ds_optimizer), ("Dt", self.dt_optimizer))
+
+    @property
+    def grad_norms(self):
+        """{"G", "Ds", "Dt"} -> device scalar (float64): the norm of the finite part of the gradient that network's last Adam
+        launch consumed (None for a network whose guard is off or that has not stepped yet).  None when no guard is configured.
+        Reading an entry on the host synchronizes; nothing here does."""
+        if not any(opt.guard for _, opt in self._optimizers()):
+            return None
+        return {tag: opt.grad_norm for tag, opt in self._optimizers()}
+
+    def guard_report(self):
+        """{"G", "Ds", "Dt"} -> host dict (optim.FlatAdam.guard_report: norm, coef, bad, skip, seen, skipped, clipped, ring rows in
+        step order; None for a network without a guard).  The only call of the guard that synchronizes.  None when no guard is
+        configured."""
+        if not any(opt.guard for _, opt in self._optimizers()):
+            return None
+        return {tag: opt.guard_report() for tag, opt in self._optimizers()}
+
     def _sync_replicas(self):
         D.broadcast_state((self.G, self.D_s, self.D_t),
                           (self.g_optimizer.flat, self.ds_optimizer.flat, self.dt_optimizer.flat))
@@ -209,8 +242,10 @@ class Trainer(object):
     # ---- trainer.py:134-176
     def select_opt_schr(self):
         betas = (self.beta1, self.beta2)
+        guard = dict(skip_nonfinite=self.skip_nonfinite, norm_log=self.grad_log)
         self.g_optimizer = FlatAdam(self.G.parameters(), self.g_lr, betas, ema_decay=self.ema_decay, ema_start=self.ema_start,
-                                    ortho=self.g_ortho, ortho_exclude=self.G.ortho_exclude() if self.g_ortho else ())
+                                    ortho=self.g_ortho, ortho_exclude=self.G.ortho_exclude() if self.g_ortho else (),
+                                    clip_norm=self.g_clip_norm, **guard)
         # (the optional attention blocks and the conditioning encoder sit at the END of the parameter order but finish their
         #  gradients late in the backward pass -- the encoder's last of all, behind the dh0 of the first ConvGRU: with them the
         #  generator's gradient goes in one piece)
@@ -224,8 +259,8 @@ class Trainer(object):
             if name.startswith("conv."):
                 self._g_bounds.setdefault(int(name.split(".")[1]), off)
             off += prm.numel()
-        self.ds_optimizer = FlatAdam(self.D_s.parameters(), self.d_lr, betas)
-        self.dt_optimizer = FlatAdam(self.D_t.parameters(), self.d_lr, betas)
+        self.ds_optimizer = FlatAdam(self.D_s.parameters(), self.d_lr, betas, clip_norm=self.d_clip_norm, **guard)
+        self.dt_optimizer = FlatAdam(self.D_t.parameters(), self.d_lr, betas, clip_norm=self.d_clip_norm, **guard)
         if self.lr_schr in ("const", "step", "exp", "multi"):
             self.g_lr_scher = _StepLR(self.g_optimizer, self.lr_schr, self.g_lr)
             self.ds_lr_scher = _StepLR(self.ds_optimizer, self.lr_schr, self.d_lr)
@@ -429,9 +464,13 @@ class Trainer(object):
             losses = self.train_step(real_videos, real_labels)
             if self.log_epoch and step % (self.log_epoch * steps_per_epoch) == 0:
                 vals = [float(v.detach()) for v in losses]
-                print("Step: [%d/%d], time: %.1fs, ds_loss: %.4f, dt_loss: %.4f, g_s_loss: %.4f, g_t_loss: %.4f, lr: %.2e"
-                      % (step, total_step, time.time() - t0, vals[0] + vals[1], vals[2] + vals[3], vals[4], vals[5],
-                         self.g_lr_scher.get_lr()[0]))
+                line = ("Step: [%d/%d], time: %.1fs, ds_loss: %.4f, dt_loss: %.4f, g_s_loss: %.4f, g_t_loss: %.4f, lr: %.2e"
+                        % (step, total_step, time.time() - t0, vals[0] + vals[1], vals[2] + vals[3], vals[4], vals[5],
+                           self.g_lr_scher.get_lr()[0]))
+                for tag, rep in (self.guard_report() or {}).items():
+                    if rep is not None:
+                        line += ", %s |g|: %.3e skipped: %d" % (tag, rep["norm"], rep["skipped"])
+                print(line)
             if self.model_save_epoch and step % (self.model_save_epoch * steps_per_epoch) == 0:
                 self.save_models(step)
 

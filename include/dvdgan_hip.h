@@ -419,6 +419,40 @@ int dvd_ema_step(float* ema, const float* p, long long n, float decay, void* str
  * no-op; buffers that overlap in part are not supported (not checked: both would be corrupted). */
 int dvd_swap_f32(float* a, float* b, long long n, void* stream);
 
+/* Gradient-norm clipping and non-finite step skipping on the device (no reference counterpart; optim.FlatAdam(clip_norm,
+ * skip_nonfinite, norm_log).step; additions: the ABI version stays 13).  Two calls per step, both asynchronous, no hidden sync:
+ *
+ * dvd_grad_guard reads the flat fp32 gradient once (two launches, no atomics).  Workgroup w owns elements [w * DVD_GUARD_CH,
+ * (w + 1) * DVD_GUARD_CH); which thread adds element i, and at which position of its order, depends on i and n only -- not on the
+ * alignment of g (16-byte aligned buffers take vector loads, others the same assignment with scalar loads), not on the grid: the
+ * result is bit-equal across alignments and reruns.  Each element enters as the exact fp64 product (double)x * (double)x; all
+ * additions are fp64, in a fixed order (thread, xor shuffles within the wave, the four waves in order, then the per-workgroup
+ * partials in a fixed order).  Elements whose exponent field is all ones (inf / NaN; an integer test on the bits) are counted and
+ * left out of the sum.  Then
+ *   norm = sqrt(S),  coef = min(1, (double)max_norm / (norm + 1e-6)),  coef32 = (float)coef     (torch's clip_grad_norm_;
+ *   exactly 1 for max_norm = +inf: measure only),  skip = skip_nonfinite && bad > 0
+ * and `state` (double[DVD_GUARD_STATE], zeroed by the caller before the first call, 8-byte aligned) receives
+ *   [0] norm of the finite part   [1] coef32 (0.0 on a skipped step)   [2] bad = number of inf / NaN elements   [3] skip (0 / 1)
+ *   [4] steps seen   [5] steps skipped   [6] steps clipped (coef32 < 1 and not skipped)   [7] 0     ([4..6] count calls).
+ * ring != NULL with ring_rows = R > 0: row (step - 1) % R of the double[R][4] log receives step, norm, coef32, bad.
+ * ws: dvd_grad_guard_ws_bytes(n) bytes, 8-byte aligned, written by every call: with W = ceil(n / DVD_GUARD_CH) workgroups,
+ * double partial[W] (sum of squares of each chunk), double S (their sum, norm = sqrt(S)), unsigned bad[W] (counts per chunk).
+ * DVD_E_ARG before any launch: g / ws / state null or state / ws not 8-byte aligned, n <= 0, step <= 0, max_norm NaN or <= 0,
+ * ring_rows < 0, ring == NULL with ring_rows > 0.  dvd_grad_guard_ws_bytes(n <= 0) = 0.
+ *
+ * dvd_adam_guard_step is dvd_adam_ema_step (ema != NULL) or dvd_adam_step's arithmetic (ema == NULL) on g[i] * coef32 -- a product
+ * rounded on its own, never fused; coef32 == 1 reproduces g[i], so the launch is then bit-equal to the unguarded one -- unless
+ * state[3] says skip: then every workgroup returns without touching p, m, v or ema.  `step` is the caller's count (bias
+ * correction): a skipped step is not taken back.  DVD_E_ARG: a null pointer other than ema, n <= 0, step <= 0, decay outside
+ * [0, 1) when ema is given.  The buffers must not overlap one another (not checked). */
+#define DVD_GUARD_CH 16384
+#define DVD_GUARD_STATE 8
+long long dvd_grad_guard_ws_bytes(long long n);
+int dvd_grad_guard(const float* g, long long n, float max_norm, int skip_nonfinite, long long step, void* ws, double* state,
+                   double* ring, int ring_rows, void* stream);
+int dvd_adam_guard_step(float* p, const float* g, float* m, float* v, float* ema /* may be NULL */, long long n, float lr,
+                        float beta1, float beta2, float eps, int step, float decay, const double* state, void* stream);
+
 /* Prediction metrics (metrics.frame_metrics, Trainer.evaluate_prediction; additions: the ABI version stays 13): per-frame MSE and
  * SSIM of F = B * T predicted frames against target frames, C channels of H x W fp32 each, 11 <= H, W <= 256.  Each operand is a
  * base pointer with batch, time and channel strides in ELEMENTS; the H x W planes are contiguous (row stride W).  So `pred` can be
