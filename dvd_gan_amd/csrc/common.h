@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include "../../include/dvdgan_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -133,6 +134,9 @@ extern "C" __attribute__((visibility("hidden"))) int dvd_conv_forward_gru(const 
 // Internal: n independent convolutions (d[i], gate epilogue g[i], mode 0 = none / 6 = direct epilogue behind the in-launch split-K
 // combine) in ONE launch of kernel `kind`; see conv_igemm.hip
 extern "C" __attribute__((visibility("hidden"))) int dvd_conv_forward_group(const dvd_conv_desc* d, const GruEpi* g, int n, int kind, int run, void* stream);
+// Internal (tests/native/stack_schedule.cpp): the recorded wavefront schedule of one pass of a ConvGRU stack as text, one line per
+// launch in issue order; see gru.hip
+extern "C" __attribute__((visibility("hidden"))) int dvd_convgru_stack_dump(const dvd_gru_stack_desc* d, int backward, FILE* out);
 // Internal: weight gradients with 3 (8) channels on one side and 64 on the other (wgrad_thin.hip); 0 floats = not served there
 long long dvd_wgrad_thin_ws_floats(const dvd_wgrad_desc* d);
 int dvd_wgrad_thin(const dvd_wgrad_desc* d, void* stream);

@@ -17,7 +17,7 @@
 #include "conv_common.h"
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -199,33 +199,6 @@ __global__ void gru_dh0_kernel(const float* carry, const float* ws, int ns, floa
     out[i] = v;
 }
 
-// recurrent conv whose epilogue applies the gate math directly (no split-K, no fp32 slabs)
-// (nsplit > 1: in-launch split-K, the tile's last workgroup to arrive runs the gate epilogue -- g.slabs / g.tickets)
-int conv_fused(int dtype, int B, int H, int W, int k, const void* in, int C, const void* w, const void* wq, int Cout, const GruEpi& g,
-               int nsplit, void* stream) {
-    dvd_conv_desc d = {};
-    d.dtype = dtype; d.frames = B; d.T = 1; d.H = H; d.W = W; d.C = C; d.ldi = C; d.Cout = Cout; d.ldo = Cout;
-    d.kt = 1; d.kh = k; d.kw = k; d.nsplit = nsplit; d.in = in; d.w = w; d.wq = wq; d.out = g.mode == 1 ? g.u : g.hn;   // (`out` itself is not written)
-    return dvd_conv_forward_gru(&d, &g, stream);
-}
-
-// backward-data conv of the BPTT whose epilogue folds the result into the carry / gate gradients (modes 3, 4)
-int conv_fused_bwd(int dtype, int B, int H, int W, int k, const void* in, int C, int ldi, const void* w, const void* wq, int Cout,
-                   const GruEpi& g, int nsplit, void* stream) {
-    dvd_conv_desc d = {};
-    d.dtype = dtype; d.frames = B; d.T = 1; d.H = H; d.W = W; d.C = C; d.ldi = ldi; d.Cout = Cout; d.ldo = Cout;
-    d.kt = 1; d.kh = k; d.kw = k; d.nsplit = nsplit; d.in = in; d.w = w; d.wq = wq; d.out = g.h32n;     // `out` itself is not written
-    return dvd_conv_forward_gru(&d, &g, stream);
-}
-
-int conv_slabs(int dtype, int B, int H, int W, int k, const void* in, int C, int ldi, const void* w, const void* wq, int Cout,
-               int nsplit, float* ws, void* stream) {
-    dvd_conv_desc d = {};
-    d.dtype = dtype; d.frames = B; d.T = 1; d.H = H; d.W = W; d.C = C; d.ldi = ldi; d.Cout = Cout; d.ldo = Cout;
-    d.kt = 1; d.kh = k; d.kw = k; d.nsplit = nsplit; d.in = in; d.w = w; d.wq = wq; d.ws = ws;
-    return dvd_conv_forward(&d, stream);
-}
-
 }  // namespace
 
 #define S_ ((hipStream_t)stream)
@@ -235,6 +208,105 @@ int conv_slabs(int dtype, int B, int H, int W, int k, const void* in, int C, int
         else if ((dtype) == DVD_F32) { using T = float; __VA_ARGS__; }         \
         else return DVD_E_ARG;                                                 \
     } while (0)
+
+namespace {
+
+// ---- one (layer, step): the pointers of its tensors, the gate epilogues and the convolution descriptor built from them.
+// dvd_convgru_layer_* and the wavefront schedule (record_forward / record_backward) both use these and nothing else.
+struct FwdStep {
+    const char* hprev;                 // h_{t-1}: the previous step's state, the supplied h0 at t = 0, or null
+    const char* gx;
+    char *u, *r, *o, *hr, *hn;         // (r, o: null in an inference-mode forward)
+    const float* h32p; float* h32n;    // fp32 carry of h, ping-pong
+};
+FwdStep fwd_step(const dvd_gru_desc& d, int t) {
+    const size_t esz = d.dtype == DVD_BF16 ? 2 : 4, Mh = (size_t)d.B * d.H * d.W * d.hidden, step = Mh * esz;
+    const size_t astep = d.infer ? 0 : step;       // inference: u / h*r are one-step scratch, r and o are not stored at all
+    FwdStep s;
+    s.hprev = t > 0 ? (const char*)d.h_all + (t - 1) * step : (const char*)d.h0;
+    s.gx = (const char*)d.gx + (size_t)t * d.gx_stride * esz;
+    s.u = (char*)d.u_all + t * astep; s.r = d.infer ? nullptr : (char*)d.r_all + t * step;
+    s.o = d.infer ? nullptr : (char*)d.o_all + t * step; s.hr = (char*)d.hr_all + t * astep;
+    s.hn = (char*)d.h_all + t * step;
+    s.h32p = (d.h32 && t > 0) ? d.h32 + (size_t)(t & 1) * Mh : nullptr;
+    s.h32n = d.h32 ? d.h32 + (size_t)((t + 1) & 1) * Mh : nullptr;
+    return s;
+}
+// modes 1 ([u|r] convolution) and 2 (out-gate convolution)
+GruEpi epi_fwd(const dvd_gru_desc& d, const FwdStep& s, int mode) {
+    GruEpi g = {};
+    g.mode = mode; g.h = d.hidden; g.ldg = 3 * d.hidden; g.gx = s.gx; g.hprev = s.hprev; g.h32p = s.h32p; g.u_in = s.u;
+    g.u = s.u; g.r = s.r; g.hr = s.hr; g.o = s.o; g.hn = s.hn; g.h32n = s.h32n;
+    return g;
+}
+
+// dh_all: [T][M][hidden] gradient wrt the layer's states from above (dvd_gru_desc.dh_out, or the x-path of the next layer of a stack), or null
+struct BwdStep { const char *hprev, *u, *r, *o, *dho; char* dg; };
+BwdStep bwd_step(const dvd_gru_desc& d, int t, const void* dh_all) {
+    const size_t esz = d.dtype == DVD_BF16 ? 2 : 4, step = (size_t)d.B * d.H * d.W * d.hidden * esz;
+    BwdStep s;
+    s.hprev = t > 0 ? (const char*)d.h_all + (t - 1) * step : (const char*)d.h0;
+    s.u = (const char*)d.u_all + t * step; s.r = (const char*)d.r_all + t * step; s.o = (const char*)d.o_all + t * step;
+    s.dho = dh_all ? (const char*)dh_all + t * step : nullptr;
+    s.dg = (char*)d.dg + t * 3 * step;
+    return s;
+}
+// mode 3: the d(h*r) convolution applies the reset-gate step
+GruEpi epi_bwd_r(const dvd_gru_desc& d, const BwdStep& s) {
+    GruEpi g = {};
+    g.mode = 3; g.h = d.hidden; g.ldg = 3 * d.hidden; g.r = const_cast<char*>(s.r); g.hprev = s.hprev; g.h32n = d.carry; g.o = s.dg;
+    return g;
+}
+// mode 4: the d[u|r] convolution of step t adds into the carry; mode 5 (t > 0): the first half of step t - 1 rides in this conv's epilogue
+GruEpi epi_bwd_ur(const dvd_gru_desc& d, int t, const void* dh_all) {
+    GruEpi g = {};
+    g.mode = 4; g.h = d.hidden; g.ldg = 3 * d.hidden; g.h32n = d.carry;
+    if (t > 0) {
+        const BwdStep p = bwd_step(d, t - 1, dh_all);
+        g.mode = 5; g.gx = p.dho; g.u_in = p.u; g.hr = const_cast<char*>(p.o); g.hprev = p.hprev; g.o = p.dg;
+    }
+    return g;
+}
+
+// a k x k convolution over the M rows of one step.  `out`: with a gate epilogue the tensor it names is not written by the conv itself;
+// `ws`: fp32 split-K slabs instead of an output (the gate kernel that follows sums them)
+dvd_conv_desc step_conv(const dvd_gru_desc& L, const void* in, int C, int ldi, const void* w, const void* wq, int Cout, int nsplit,
+                        void* out, float* ws = nullptr) {
+    dvd_conv_desc d = {};
+    d.dtype = L.dtype; d.frames = L.B; d.T = 1; d.H = L.H; d.W = L.W; d.C = C; d.ldi = ldi; d.Cout = Cout; d.ldo = Cout;
+    d.kt = 1; d.kh = L.k; d.kw = L.k; d.nsplit = nsplit; d.in = in; d.w = w; d.wq = wq; d.wq_kind = 1; d.out = out; d.ws = ws;
+    return d;
+}
+
+// the elementwise gate kernels: all of a step when its convolution is absent (no previous state) or left slabs, the first BPTT step, dh0
+enum GateKernel { GK_GATES_UR, GK_OUT, GK_BWD_OUT, GK_BWD_R, GK_DH0 };
+const char* const kGateKernelName[] = {"gates_ur", "out", "bwd_out", "bwd_r", "dh0"};
+int gate_kernel(int which, const dvd_gru_desc& d, int t, const void* dh_all, const float* ws, int ns, void* stream) {
+    const int h = d.hidden;
+    const long long M = (long long)d.B * d.H * d.W;
+    const unsigned grid = cdiv(M * (h / 8), 256);
+    if (which == GK_GATES_UR || which == GK_OUT) {
+        const FwdStep s = fwd_step(d, t);
+        if (which == GK_GATES_UR)
+            BY_DTYPE(d.dtype, gru_gates_ur_kernel<T><<<grid, 256, 0, S_>>>(ws, ns, (const T*)s.gx, 3 * h, (const T*)s.hprev, (T*)s.u, (T*)s.r,
+                                                                            (T*)s.hr, M, h));
+        else
+            BY_DTYPE(d.dtype, gru_out_kernel<T><<<grid, 256, 0, S_>>>(ws, ns, (const T*)s.gx, 3 * h, (const T*)s.hprev, s.h32p, (const T*)s.u,
+                                                                       (T*)s.o, (T*)s.hn, s.h32n, M, h));
+    } else if (which == GK_DH0) {
+        gru_dh0_kernel<<<cdiv(M * h, 256), 256, 0, S_>>>(d.carry, ws, ns, d.dh0, M, h);
+    } else {
+        const BwdStep s = bwd_step(d, t, dh_all);
+        if (which == GK_BWD_OUT)
+            BY_DTYPE(d.dtype, gru_bwd_out_kernel<T><<<grid, 256, 0, S_>>>((const T*)s.dho, d.carry, ws, ns, (const T*)s.u, (const T*)s.o,
+                                                                           (const T*)s.hprev, (T*)s.dg, 3 * h, M, h));
+        else
+            BY_DTYPE(d.dtype, gru_bwd_r_kernel<T><<<grid, 256, 0, S_>>>(d.carry, ws, ns, (const T*)s.r, (const T*)s.hprev, (T*)s.dg, 3 * h, M, h));
+    }
+    return DVD_OK;
+}
+
+}  // namespace
 
 // Split-K factor that brings a conv with few output tiles up to ~two workgroups per CU (measured on the
 // full step: target 128 -> 948 ms, 256 -> 922, 384 -> 917, 512 -> 913; re-swept with the halo kernels, where a split
@@ -272,9 +344,7 @@ extern "C" int dvd_conv_pick_nsplit(int dtype, long long M, int Cout, int C, int
 // slabs by ONE workgroup per tile costs more than the gate kernel, which spreads the same reads over the whole chip (S = 4:
 // 33.9 / 35.9 -> 37.9 / 39.4, 67.3 / 69.6 -> 72.6 / 80.3).  Fewer, longer slices so that everything combines in-launch lose as well
 // (at most 2 slices everywhere: the S = 4 / 8 layers 56.4 -> 70.4 ms over a pass pair).  dvd_gru_desc.combine_max overrides the 4.
-static int inlaunch_max() {
-    return 4;
-}
+constexpr int kInlaunchMax = 4;
 
 // floats of dvd_gru_desc.ws: nsplit slabs of whole output tiles (up to 256 rows x 256 columns) for the widest of the three
 // recurrent convolutions of a layer
@@ -294,62 +364,45 @@ static int capped_nsplit(const dvd_gru_desc* d, long long M, int Cout, int C, in
     const int ns = dvd_conv_pick_nsplit(d->dtype, M, Cout, C, ntaps);
     return (d->ns_cap > 0 && ns > d->ns_cap) ? d->ns_cap : ns;
 }
+// shape rules common to both passes of the layer path
+static int layer_check(const dvd_gru_desc* d) {
+    if (d->T <= 0 || d->B <= 0 || d->hidden <= 0 || !(d->k & 1)) return DVD_E_ARG;
+    if (d->hidden & 7) return DVD_E_SHAPE;
+    if ((long long)d->B * d->H * d->W * (d->hidden / 8) >= (1ll << 31)) return DVD_E_SHAPE;
+    return DVD_OK;
+}
+// One recurrent convolution of the layer path.  `fused`: the gate math runs in its epilogue (split-K: by the tile's last workgroup);
+// otherwise it leaves `ns` fp32 slabs in d->ws for the gate kernel that follows -- none when the step has no previous state.
+static int layer_conv(const dvd_gru_desc* d, dvd_conv_desc c, GruEpi g, bool has_prev, bool fused, int& ns, void* stream) {
+    ns = 0;
+    if (!has_prev) return DVD_OK;
+    if (fused) {
+        g.slabs = d->ws; g.tickets = d->tickets;
+        return dvd_conv_forward_gru(&c, &g, stream);
+    }
+    ns = c.nsplit; c.out = nullptr; c.ws = d->ws;
+    return dvd_conv_forward(&c, stream);
+}
 
 extern "C" int dvd_convgru_layer_forward(const dvd_gru_desc* d, void* stream) {
     if (!d || !d->gx || !d->w_ur || !d->w_o || !d->h_all || !d->u_all || !d->hr_all || !d->ws) return DVD_E_ARG;
     if (!d->infer && (!d->r_all || !d->o_all)) return DVD_E_ARG;
-    if (d->T <= 0 || d->B <= 0 || d->hidden <= 0 || !(d->k & 1)) return DVD_E_ARG;
-    if (d->hidden & 7) return DVD_E_SHAPE;
+    if (int rc = layer_check(d)) return rc;
     const int h = d->hidden, ntaps = d->k * d->k;
     const long long M = (long long)d->B * d->H * d->W;
-    if (M * (d->hidden / 8) >= (1ll << 31)) return DVD_E_SHAPE;
-    const size_t esz = d->dtype == DVD_BF16 ? 2 : 4;
-    const size_t step = (size_t)M * h * esz;
-    const size_t astep = d->infer ? 0 : step;       // inference: u / h*r are one-step scratch, r and o are not stored at all
     const int ns_ur = capped_nsplit(d, M, 2 * h, h, ntaps);
     const int ns_o = capped_nsplit(d, M, h, h, ntaps);
-    const int nmax = !d->tickets ? 1 : d->combine_max > 0 ? d->combine_max : inlaunch_max();    // convs with up to nmax slices apply the gates in their epilogue
-    const unsigned grid = cdiv(M * (h / 8), 256);
+    const int nmax = !d->tickets ? 1 : d->combine_max > 0 ? d->combine_max : kInlaunchMax;    // convs with up to nmax slices apply the gates in their epilogue
     for (int t = 0; t < d->T; ++t) {
-        const char* hprev = t > 0 ? (const char*)d->h_all + (t - 1) * step : (const char*)d->h0;
-        const char* gx = (const char*)d->gx + (size_t)t * d->gx_stride * esz;
-        char* u = (char*)d->u_all + t * astep; char* r = d->infer ? nullptr : (char*)d->r_all + t * step;
-        char* o = d->infer ? nullptr : (char*)d->o_all + t * step; char* hr = (char*)d->hr_all + t * astep;
-        char* hn = (char*)d->h_all + t * step;
-        const float* h32p = (d->h32 && t > 0) ? d->h32 + (size_t)(t & 1) * M * h : nullptr;
-        float* h32n = d->h32 ? d->h32 + (size_t)((t + 1) & 1) * M * h : nullptr;
-        int rc, ns = 0;
-        GruEpi g = {};
-        g.h = h; g.ldg = 3 * h; g.gx = gx; g.hprev = hprev; g.h32p = h32p; g.u_in = u;
-        g.u = u; g.r = r; g.hr = hr; g.o = o; g.hn = hn; g.h32n = h32n;
-        g.slabs = d->ws; g.tickets = d->tickets;
-        if (hprev && ns_ur <= nmax) {                 // gates applied in the conv epilogue (split-K: by the tile's last workgroup)
-            g.mode = 1;
-            rc = conv_fused(d->dtype, d->B, d->H, d->W, d->k, hprev, h, d->w_ur, d->w_ur_q, 2 * h, g, ns_ur, stream);
-            if (rc) return rc;
-        } else {
-            if (hprev) {
-                rc = conv_slabs(d->dtype, d->B, d->H, d->W, d->k, hprev, h, h, d->w_ur, d->w_ur_q, 2 * h, ns_ur, d->ws, stream);
-                if (rc) return rc;
-                ns = ns_ur;
-            }
-            BY_DTYPE(d->dtype, gru_gates_ur_kernel<T><<<grid, 256, 0, S_>>>(d->ws, ns, (const T*)gx, 3 * h,
-                                                                            (const T*)hprev, (T*)u, (T*)r, (T*)hr, M, h));
-        }
-        ns = 0;
-        if (hprev && ns_o <= nmax) {
-            g.mode = 2;
-            rc = conv_fused(d->dtype, d->B, d->H, d->W, d->k, hr, h, d->w_o, d->w_o_q, h, g, ns_o, stream);
-            if (rc) return rc;
-        } else {
-            if (hprev) {
-                rc = conv_slabs(d->dtype, d->B, d->H, d->W, d->k, hr, h, h, d->w_o, d->w_o_q, h, ns_o, d->ws, stream);
-                if (rc) return rc;
-                ns = ns_o;
-            }
-            BY_DTYPE(d->dtype, gru_out_kernel<T><<<grid, 256, 0, S_>>>(d->ws, ns, (const T*)gx, 3 * h, (const T*)hprev,
-                                                                       h32p, (const T*)u, (T*)o, (T*)hn, h32n, M, h));
-        }
+        const FwdStep s = fwd_step(*d, t);
+        const bool prev = s.hprev != nullptr, fuse_ur = prev && ns_ur <= nmax, fuse_o = prev && ns_o <= nmax;
+        int rc, ns;
+        rc = layer_conv(d, step_conv(*d, s.hprev, h, h, d->w_ur, d->w_ur_q, 2 * h, ns_ur, s.u), epi_fwd(*d, s, 1), prev, fuse_ur, ns, stream);
+        if (!rc && !fuse_ur) rc = gate_kernel(GK_GATES_UR, *d, t, nullptr, d->ws, ns, stream);
+        if (rc) return rc;
+        rc = layer_conv(d, step_conv(*d, s.hr, h, h, d->w_o, d->w_o_q, h, ns_o, s.hn), epi_fwd(*d, s, 2), prev, fuse_o, ns, stream);
+        if (!rc && !fuse_o) rc = gate_kernel(GK_OUT, *d, t, nullptr, d->ws, ns, stream);
+        if (rc) return rc;
     }
     return launch_status();
 }
@@ -357,75 +410,34 @@ extern "C" int dvd_convgru_layer_forward(const dvd_gru_desc* d, void* stream) {
 extern "C" int dvd_convgru_layer_backward(const dvd_gru_desc* d, void* stream) {
     if (!d || !d->wd_ur || !d->wd_o || !d->h_all || !d->u_all || !d->r_all || !d->o_all || !d->dg || !d->carry || !d->ws)
         return DVD_E_ARG;
-    if (d->T <= 0 || d->B <= 0 || d->hidden <= 0 || !(d->k & 1)) return DVD_E_ARG;
-    if (d->hidden & 7) return DVD_E_SHAPE;
+    if (int rc = layer_check(d)) return rc;
     const int h = d->hidden, ntaps = d->k * d->k;
     const long long M = (long long)d->B * d->H * d->W;
-    if (M * (d->hidden / 8) >= (1ll << 31)) return DVD_E_SHAPE;
     const size_t esz = d->dtype == DVD_BF16 ? 2 : 4;
-    const size_t step = (size_t)M * h * esz;
     const int ns_o = capped_nsplit(d, M, h, h, ntaps);        // d(hr)  = convT(d pre_o)
     const int ns_ur = capped_nsplit(d, M, h, 2 * h, ntaps);   // dh    += convT(d pre_u | d pre_r)
-    const int nmax = !d->tickets ? 1 : d->combine_max > 0 ? d->combine_max : inlaunch_max();
-    const unsigned grid = cdiv(M * (h / 8), 256);
+    const int nmax = !d->tickets ? 1 : d->combine_max > 0 ? d->combine_max : kInlaunchMax;
     hipError_t e = hipMemsetAsync(d->carry, 0, (size_t)M * h * sizeof(float), S_);
     if (e != hipSuccess) return DVD_E_LAUNCH;
     int ns_pending = 0;      // slabs of the ur backward-data conv of step t+1 waiting in ws
     bool out_done = false;   // first half of this step already applied by the previous step's conv epilogue (mode 5)
     for (int t = d->T - 1; t >= 0; --t) {
-        const char* hprev = t > 0 ? (const char*)d->h_all + (t - 1) * step : (const char*)d->h0;
-        const char* u = (const char*)d->u_all + t * step; const char* r = (const char*)d->r_all + t * step;
-        const char* o = (const char*)d->o_all + t * step;
-        const char* dho = d->dh_out ? (const char*)d->dh_out + t * step : nullptr;
-        char* dg = (char*)d->dg + (size_t)t * M * 3 * h * esz;
-        if (!out_done)
-            BY_DTYPE(d->dtype, gru_bwd_out_kernel<T><<<grid, 256, 0, S_>>>((const T*)dho, d->carry, d->ws, ns_pending,
-                                                                           (const T*)u, (const T*)o, (const T*)hprev,
-                                                                           (T*)dg, 3 * h, M, h));
-        ns_pending = 0;
-        out_done = false;
-        int ns = 0, rc;
-        GruEpi g = {};
-        g.h = h; g.ldg = 3 * h; g.r = const_cast<char*>(r); g.hprev = hprev; g.h32n = d->carry; g.o = dg;
-        g.slabs = d->ws; g.tickets = d->tickets;
-        if (hprev && ns_o <= nmax) {                  // d(h*r) conv applies the reset-gate step in its epilogue
-            g.mode = 3;
-            rc = conv_fused_bwd(d->dtype, d->B, d->H, d->W, d->k, dg + (size_t)2 * h * esz, h, 3 * h, d->wd_o, d->wd_o_q, h, g, ns_o,
-                                stream);
-            if (rc) return rc;
-        } else {
-            if (hprev) {
-                rc = conv_slabs(d->dtype, d->B, d->H, d->W, d->k, dg + (size_t)2 * h * esz, h, 3 * h, d->wd_o, d->wd_o_q, h, ns_o, d->ws,
-                                stream);
-                if (rc) return rc;
-                ns = ns_o;
-            }
-            BY_DTYPE(d->dtype, gru_bwd_r_kernel<T><<<grid, 256, 0, S_>>>(d->carry, d->ws, ns, (const T*)r, (const T*)hprev,
-                                                                         (T*)dg, 3 * h, M, h));
-        }
-        if (hprev) {
-            if (ns_ur <= nmax) {             // [u|r] backward-data conv adds straight into the carry and goes on with
-                g.mode = 4;                  // the first half of step t-1 (mode 5) unless this is step 0 with an h0
-                if (t > 0) {
-                    const size_t tp = (size_t)(t - 1);
-                    g.mode = 5;
-                    g.gx = d->dh_out ? (const char*)d->dh_out + tp * step : nullptr;
-                    g.u_in = (const char*)d->u_all + tp * step;
-                    g.hr = const_cast<char*>((const char*)d->o_all + tp * step);
-                    g.hprev = t - 1 > 0 ? (const char*)d->h_all + (tp - 1) * step : (const char*)d->h0;
-                    g.o = (char*)d->dg + tp * M * 3 * h * esz;
-                    out_done = true;
-                }
-                rc = conv_fused_bwd(d->dtype, d->B, d->H, d->W, d->k, dg, 2 * h, 3 * h, d->wd_ur, d->wd_ur_q, h, g, ns_ur, stream);
-                if (rc) return rc;
-            } else {
-                rc = conv_slabs(d->dtype, d->B, d->H, d->W, d->k, dg, 2 * h, 3 * h, d->wd_ur, d->wd_ur_q, h, ns_ur, d->ws, stream);
-                if (rc) return rc;
-                ns_pending = ns_ur;
-            }
-        }
+        const BwdStep s = bwd_step(*d, t, d->dh_out);
+        const bool prev = s.hprev != nullptr, fuse_o = prev && ns_o <= nmax, fuse_ur = prev && ns_ur <= nmax;
+        int rc = DVD_OK, ns;
+        if (!out_done) rc = gate_kernel(GK_BWD_OUT, *d, t, d->dh_out, d->ws, ns_pending, stream);
+        if (rc) return rc;
+        rc = layer_conv(d, step_conv(*d, s.dg + (size_t)2 * h * esz, h, 3 * h, d->wd_o, d->wd_o_q, h, ns_o, d->carry), epi_bwd_r(*d, s), prev,
+                        fuse_o, ns, stream);
+        if (!rc && !fuse_o) rc = gate_kernel(GK_BWD_R, *d, t, d->dh_out, d->ws, ns, stream);
+        if (rc) return rc;
+        // the [u|r] backward-data conv adds straight into the carry and goes on with the first half of step t-1 unless this is step 0 with an h0
+        rc = layer_conv(d, step_conv(*d, s.dg, 2 * h, 3 * h, d->wd_ur, d->wd_ur_q, h, ns_ur, d->carry), epi_bwd_ur(*d, t, d->dh_out), prev,
+                        fuse_ur, ns_pending, stream);
+        if (rc) return rc;
+        out_done = fuse_ur && t > 0;
     }
-    if (d->dh0) gru_dh0_kernel<<<cdiv(M * h, 256), 256, 0, S_>>>(d->carry, d->ws, ns_pending, d->dh0, M, h);
+    if (d->dh0) gate_kernel(GK_DH0, *d, 0, nullptr, d->ws, ns_pending, stream);
     return launch_status();
 }
 
@@ -440,13 +452,28 @@ extern "C" int dvd_convgru_layer_backward(const dvd_gru_desc* d, void* stream) {
 //             step t (all three gate gradients of the step are complete), whose result is layer l-1's dh_out of step t -- needed by
 //             layer l-1's B convolution of step t + 1 in pair k + 1.
 // The steps without a previous state (t = 0, no h0) and the first BPTT step of a layer run the elementwise gate kernels.
-#ifndef DVD_STACK_SEARCH_KINDS
-#define DVD_STACK_SEARCH_KINDS(kind) 1
-#endif
+//
+// A pass is RECORDED first (record_forward / record_backward: every launch in issue order, every member's descriptor, epilogue,
+// split-K factor and slab offset) and then PLAYED (play).  The sizing query reads the same record, so a launch can only use slab
+// offsets the caller was told about; a stack whose record holds a group of more than kGroupMax members is not served at all.
 namespace {
 
-struct Member { dvd_conv_desc d; long long tiles; int kchunks; int gate; };
-// debug bookkeeping behind dvd_debug_stack_ws (tests only): the last sizing answer and the largest slab cursor a LAUNCHED group used
+struct Member { dvd_conv_desc d; GruEpi g; long long tiles; int kchunks; int gate; };
+struct Launch {
+    int kind;                 // >= 0: grouped launch of kGroupKind[kind], members [first, first + n) of Schedule::d / g; -1: gate kernel
+    int first, n;
+    long long ws_end;         // slab cursor behind the group's last member
+    int which, layer, t;      // gate kernel: GateKernel, its layer and step
+};
+struct Schedule {
+    bool backward = false;
+    std::vector<Launch> ops;
+    std::vector<dvd_conv_desc> d;
+    std::vector<GruEpi> g;
+    long long ws_floats = 0;  // largest slab cursor of any group
+    int max_members = 0;
+};
+// debug bookkeeping behind dvd_debug_stack_ws (tests only): the last sizing answer and the largest slab cursor a PLAYED group used
 std::atomic<long long> g_ws_sized{0}, g_ws_high{0};
 constexpr int kMaxMember = 2 * DVD_GRU_STACK_MAX;
 
@@ -461,37 +488,16 @@ int stack_kind(const dvd_gru_stack_desc* s) {
     for (int l = 0; l < s->n_layers; ++l) t256 += (long long)cdiv(a.B, 4) * cdiv(2 * s->layer[l].hidden, 128);
     return t256 >= 256 ? 2 : 3;
 }
-int stack_check(const dvd_gru_stack_desc* s, bool backward) {
-    if (!s || s->n_layers < 1 || s->n_layers > DVD_GRU_STACK_MAX) return DVD_E_ARG;
-    const dvd_gru_desc& a = s->layer[0];
-    if (a.dtype != DVD_BF16 || a.T <= 0 || a.B <= 0 || !a.tickets || !s->ws) return DVD_E_ARG;
-    if (stack_kind(s) < 0) return DVD_E_SHAPE;
-    for (int l = 0; l < s->n_layers; ++l) {
-        const dvd_gru_desc& d = s->layer[l];
-        if (d.dtype != a.dtype || d.T != a.T || d.B != a.B || d.H != a.H || d.W != a.W) return DVD_E_ARG;
-        if (d.hidden <= 0 || (d.hidden & 7) || (d.k != 3 && d.k != 5)) return DVD_E_SHAPE;
-        if ((long long)d.B * d.H * d.W * (d.hidden / 8) >= (1ll << 31)) return DVD_E_SHAPE;
-        if (!d.gx || !d.h_all || !d.u_all || !d.hr_all) return DVD_E_ARG;
-        if (l > 0 && (s->cin[l] != s->layer[l - 1].hidden || d.gx_stride != (long long)d.B * d.H * d.W * 3 * d.hidden)) return DVD_E_ARG;
-        if (!backward) {
-            if (!d.w_ur || !d.w_o || !d.w_ur_q || !d.w_o_q) return DVD_E_ARG;
-            if (!d.infer && (!d.r_all || !d.o_all)) return DVD_E_ARG;
-            if (l > 0 && (!s->wx[l] || !s->wx_q[l] || !s->bx[l])) return DVD_E_ARG;
-        } else {
-            if (!d.wd_ur || !d.wd_o || !d.wd_ur_q || !d.wd_o_q || !d.r_all || !d.o_all || !d.dg || !d.carry) return DVD_E_ARG;
-            if (l > 0 && (!s->wdx[l] || !s->wdx_q[l] || !s->dh_mid[l])) return DVD_E_ARG;
-        }
-    }
-    return DVD_OK;
-}
 
-void member_conv(Member& m, const dvd_gru_desc& L, const void* in, int C, int ldi, const void* w, const void* wq, int Cout, int kind) {
-    m = Member{};
-    dvd_conv_desc& d = m.d;
-    d.dtype = L.dtype; d.frames = L.B; d.T = 1; d.H = L.H; d.W = L.W; d.C = C; d.ldi = ldi; d.Cout = Cout; d.ldo = Cout;
-    d.kt = 1; d.kh = L.k; d.kw = L.k; d.nsplit = 1; d.in = in; d.w = w; d.wq = wq; d.wq_kind = 1;
+Member member(const dvd_gru_desc& L, int kind, const void* in, int C, int ldi, const void* w, const void* wq, int Cout, void* out,
+              const GruEpi& g = GruEpi{}) {
+    Member m = {};
+    m.d = step_conv(L, in, C, ldi, w, wq, Cout, 1, out);
+    m.g = g;
+    m.gate = g.mode != 0;
     m.tiles = (long long)cdiv((long long)L.B * L.H * L.W, kGroupKind[kind].rows) * cdiv(Cout, 128);
     m.kchunks = (C + 31) / 32;
+    return m;
 }
 
 // ---- split-K factors of a grouped launch: a search over per-member factors against a model of the launch.
@@ -540,17 +546,13 @@ SplitPlan plan_splits(int kind, bool backward, int n, const Member* m, long long
     // fitted on tools/gru_microbench.py stack (B = 64; K steps of the launch's tile shape): a split tile is cheap on 4 x 4 frames
     // (64 KB slabs, few tiles) and dear on 256-row tiles (128 KB slabs; the tile's last workgroup combines, then runs the epilogue):
     // 8 x 8 forward 13.85 -> 12.87 ms with only the 5 x 5 layer split, 4 x 4 5.39 / 6.09 -> 5.03 / 5.56, 16 x 16 backward 46.1 -> 45.0
-    double fixed = kGroupKind[kind].rows == 256 ? 12.0 : 16.0;
-    double split_cost = kind == 4 ? 3.0 : kind == 0 ? 150.0 : backward ? 50.0 : 80.0;
-#ifdef DVD_STACK_SEARCH_DEBUG
-    if (const char* e = getenv("DVD_SS_FIXED")) fixed = atof(e);
-    if (const char* e = getenv("DVD_SS_SPLIT")) split_cost = atof(e);
-#endif
+    const double fixed = kGroupKind[kind].rows == 256 ? 12.0 : 16.0;
+    const double split_cost = kind == 4 ? 3.0 : kind == 0 ? 150.0 : backward ? 50.0 : 80.0;
     static const int opts[] = {1, 2, 3, 4, 8};
     SplitPlan best{}; double best_t = 1e30;
     int idx[2 * DVD_GRU_STACK_MAX] = {0};
     if (n > 5) {
-        // 5^n combinations stop being "a few ms once" beyond five members (four-layer stacks: 7-8 members = 78 k - 390 k makespan
+        // 5^n combinations stop being "a few ms once" beyond five members (a four-layer stack's six-member groups: 15.6 k makespan
         // simulations under the lock): coordinate descent from the unsplit plan -- one member's factor at a time, until no change helps
         int ns[2 * DVD_GRU_STACK_MAX];
         for (int i = 0; i < n; ++i) ns[i] = 1;
@@ -583,39 +585,23 @@ SplitPlan plan_splits(int kind, bool backward, int n, const Member* m, long long
         while (j < n && ++idx[j] == (int)(sizeof opts / sizeof opts[0])) idx[j++] = 0;
         if (j == n) break;
     }
-#ifdef DVD_STACK_SEARCH_DEBUG
-    {
-        int one[2 * DVD_GRU_STACK_MAX]; for (int i = 0; i < n; ++i) one[i] = 1;
-        fprintf(stderr, "plan kind %d %s:", kind, backward ? "bwd" : "fwd");
-        for (int i = 0; i < n; ++i) fprintf(stderr, " [tiles %lld units %d cap %d -> ns %d]", tiles[i], units[i], capi[i], best.ns[i]);
-        fprintf(stderr, "  model %.0f (unsplit %.0f)\n", best_t, model_makespan(n, tiles, units, one, slots, fixed, split_cost));
-    }
-#endif
     cache[key] = best;
     return best;
 }
 
-// Split-K factors of one grouped launch and the slab space behind them; launches unless `dry`.
-int run_group(const dvd_gru_stack_desc* s, int kind, Member* m, GruEpi* g, int n, void* stream, bool dry, long long& ws_need, bool backward) {
-    if (n == 0) return DVD_OK;
-    long long total = 0;
-    for (int i = 0; i < n; ++i) total += m[i].tiles;
+// Records one grouped launch: the split-K factor of every member and the slab space behind it.  (A group past kGroupMax members is
+// only counted: no launch exists for it, and stack_check refuses the stack.)
+void record_group(Schedule& sc, const dvd_gru_stack_desc* s, int kind, Member* m, int n) {
+    if (n > sc.max_members) sc.max_members = n;
+    if (n == 0 || n > kGroupMax) return;
     // measured (tools/gru_microbench.py stack, B = 64): (target, cap) = (768, 4) 5.46 / 6.99 ms forward / backward on 4 x 4 frames,
     // (768, 8) 5.66 / 6.16; 8 x 8 frames: (768, 4) 14.86 / 15.09, (768, 8) 14.93 / 15.95, (384, 4) 14.46 / 16.53, (1536, *) slower
-    const long long cap = (kind == 4 && backward) ? 8 : 4;
-    const long long target = 8 * kGroupKind[kind].slots;            // the measured 512 : 768 (that they equal the slots of eight XCDs is how the table states them, not a derivation)
-    long long want = (target + total - 1) / total;
-    if (want > cap) want = cap;
+    const long long cap = (kind == 4 && sc.backward) ? 8 : 4;
     SplitPlan plan{};
-    bool searched = !s->layer_policy && DVD_STACK_SEARCH_KINDS(kind);
-#ifdef DVD_STACK_SEARCH_DEBUG
-    if (const char* e = getenv("DVD_SS_MASK")) searched = searched && ((atoi(e) >> kind) & 1) && ((atoi(e) >> (backward ? 9 : 8)) & 1);
-#endif
-    if (searched) plan = plan_splits(kind, backward, n, m, cap);
+    if (!s->layer_policy) plan = plan_splits(kind, sc.backward, n, m, cap);
     long long cursor = 0;
-    dvd_conv_desc d[kMaxMember];
     for (int i = 0; i < n; ++i) {
-        long long ns = searched ? plan.ns[i] : want;
+        long long ns = plan.ns[i];
         if (s->layer_policy)
             ns = m[i].gate ? dvd_conv_pick_nsplit(DVD_BF16, (long long)m[i].d.frames * m[i].d.H * m[i].d.W, m[i].d.Cout, m[i].d.C,
                                                   m[i].d.kh * m[i].d.kw) : 1;
@@ -624,199 +610,147 @@ int run_group(const dvd_gru_stack_desc* s, int kind, Member* m, GruEpi* g, int n
         if (ns > 1 && m[i].tiles > 1024) ns = 1;
         m[i].d.nsplit = (int)ns;
         if (ns > 1) {
-            if (g[i].mode == 0) g[i].mode = 6;            // direct epilogue behind the in-launch combine
-            g[i].slabs = s->ws + cursor; g[i].tickets = s->layer[0].tickets;
+            if (m[i].g.mode == 0) m[i].g.mode = 6;            // direct epilogue behind the in-launch combine
+            m[i].g.slabs = s->ws + cursor; m[i].g.tickets = s->layer[0].tickets;
             cursor += ns * m[i].tiles * kGroupKind[kind].tile_floats;      // accumulators of one output tile
         }
-        d[i] = m[i].d;
+        sc.d.push_back(m[i].d);
+        sc.g.push_back(m[i].g);
     }
-    if (dry) {
-        if (cursor > ws_need) ws_need = cursor;
-        return DVD_OK;
-    }
-    for (long long seen = g_ws_high.load(); cursor > seen && !g_ws_high.compare_exchange_weak(seen, cursor);) {}
-    if (cursor > ws_need) return DVD_E_SHAPE;      // (cannot happen: the launch walks the schedule the sizing query walked -- but a slab overrun is a memory fault)
-    return dvd_conv_forward_group(d, g, n, kind, s->run, stream);
+    if (cursor > sc.ws_floats) sc.ws_floats = cursor;
+    sc.ops.push_back(Launch{kind, (int)sc.d.size() - n, n, cursor, 0, 0, 0});
 }
+void record_gate(Schedule& sc, int which, int layer, int t) { sc.ops.push_back(Launch{-1, 0, 0, 0, which, layer, t}); }
 
-int stack_forward(const dvd_gru_stack_desc* s, void* stream, bool dry, long long& ws_need) {
+// gradient wrt layer l's states, [T][M][hidden_l]: from outside the stack (top layer) or from the x-path of the layer above
+const void* stack_dh(const dvd_gru_stack_desc* s, int l) { return l == s->n_layers - 1 ? s->layer[l].dh_out : s->dh_mid[l + 1]; }
+
+void record_forward(const dvd_gru_stack_desc* s, Schedule& sc) {
     const int L = s->n_layers, T = s->layer[0].T, kind = stack_kind(s);
-    const long long M = (long long)s->layer[0].B * s->layer[0].H * s->layer[0].W;
-    const size_t esz = 2;
-    for (int k = 0; k < T + 2 * (L - 1); ++k) {
-        Member mem[kMaxMember];
-        GruEpi epi[kMaxMember];
+    // bit l: the x-part of layer l rides in the U group instead of the O group (both are behind its producer).  Measured
+    // (tools/gru_microbench.py stack): no difference beyond noise except on 8 x 8 frames, where the top layer's x-part in the
+    // U group balances the two launches of a pair (14.63 -> 13.93 ms forward, 15.77 -> 14.76 backward)
+    const int x_in_u = s->layer[0].H == 8 ? 4 : 0;
+    for (int k = 0; k < T + 2 * (L - 1); ++k)
         for (int phase = 0; phase < 2; ++phase) {                 // 0 = U group, 1 = O group
+            Member mem[kMaxMember];
             int n = 0;
             for (int l = 0; l < L; ++l) {
                 const dvd_gru_desc& d = s->layer[l];
                 const int t = k - 2 * l, h = d.hidden;
                 if (t < 0 || t >= T) continue;
-                const size_t step = (size_t)M * h * esz, astep = d.infer ? 0 : step;
-                const char* hprev = t > 0 ? (const char*)d.h_all + (t - 1) * step : (const char*)d.h0;
-                const char* gx = (const char*)d.gx + (size_t)t * d.gx_stride * esz;
-                char* u = (char*)d.u_all + t * astep; char* r = d.infer ? nullptr : (char*)d.r_all + t * step;
-                char* o = d.infer ? nullptr : (char*)d.o_all + t * step; char* hr = (char*)d.hr_all + t * astep;
-                char* hn = (char*)d.h_all + t * step;
-                const float* h32p = (d.h32 && t > 0) ? d.h32 + (size_t)(t & 1) * M * h : nullptr;
-                float* h32n = d.h32 ? d.h32 + (size_t)((t + 1) & 1) * M * h : nullptr;
-                const unsigned grid = cdiv(M * (h / 8), 256);
-                const bool has_prev = t > 0 || d.h0 != nullptr;             // (the dry run sizes the workspace for exactly this schedule)
-                if (!has_prev) {                                  // step 0 without a supplied state: gates of the x-part alone
-                    if (dry) continue;
-                    using T_ = bf16_t;
-                    if (phase == 0)
-                        gru_gates_ur_kernel<T_><<<grid, 256, 0, S_>>>(nullptr, 0, (const T_*)gx, 3 * h, (const T_*)nullptr, (T_*)u, (T_*)r, (T_*)hr, M, h);
-                    else
-                        gru_out_kernel<T_><<<grid, 256, 0, S_>>>(nullptr, 0, (const T_*)gx, 3 * h, (const T_*)nullptr, h32p, (const T_*)u, (T_*)o,
-                                                                 (T_*)hn, h32n, M, h);
+                if (t == 0 && !d.h0) {                            // step 0 without a supplied state: gates of the x-part alone
+                    record_gate(sc, phase == 0 ? GK_GATES_UR : GK_OUT, l, t);
                     continue;
                 }
-                GruEpi& g = epi[n];
-                g = GruEpi{};
-                g.h = h; g.ldg = 3 * h; g.gx = gx; g.hprev = hprev; g.h32p = h32p; g.u_in = u;
-                g.u = u; g.r = r; g.hr = hr; g.o = o; g.hn = hn; g.h32n = h32n;
-                if (phase == 0) {
-                    g.mode = 1;
-                    member_conv(mem[n], d, hprev, h, h, d.w_ur, d.w_ur_q, 2 * h, kind);
-                    mem[n].d.out = u;
-                } else {
-                    g.mode = 2;
-                    member_conv(mem[n], d, hr, h, h, d.w_o, d.w_o_q, h, kind);
-                    mem[n].d.out = hn;
-                }
-                mem[n].gate = 1;
-                ++n;
+                const FwdStep st = fwd_step(d, t);
+                mem[n++] = phase == 0 ? member(d, kind, st.hprev, h, h, d.w_ur, d.w_ur_q, 2 * h, st.u, epi_fwd(d, st, 1))
+                                      : member(d, kind, st.hr, h, h, d.w_o, d.w_o_q, h, st.hn, epi_fwd(d, st, 2));
             }
-            // bit l: the x-part of layer l rides in the U group instead of the O group (both are behind its producer).  Measured
-            // (tools/gru_microbench.py stack): no difference beyond noise except on 8 x 8 frames, where the top layer's x-part in the
-            // U group balances the two launches of a pair (14.63 -> 13.93 ms forward, 15.77 -> 14.76 backward)
-            const int x_in_u = s->layer[0].H == 8 ? 4 : 0;
             for (int l = 1; l < L; ++l)
                 if (phase == (((x_in_u >> l) & 1) ? 0 : 1)) {     // x-part of layer l for step k - 2 l + 1
                     const dvd_gru_desc& d = s->layer[l];
-                    const dvd_gru_desc& b = s->layer[l - 1];
-                    const int t = k - 2 * l + 1;
+                    const int t = k - 2 * l + 1, ci = s->layer[l - 1].hidden;
                     if (t < 0 || t >= T) continue;
-                    epi[n] = GruEpi{};
-                    member_conv(mem[n], d, (const char*)b.h_all + (size_t)t * M * b.hidden * esz, b.hidden, b.hidden, s->wx[l], s->wx_q[l],
-                                3 * d.hidden, kind);
-                    mem[n].d.bias = s->bx[l];
-                    mem[n].d.out = (char*)d.gx + (size_t)t * d.gx_stride * esz;
-                    ++n;
+                    mem[n] = member(d, kind, fwd_step(s->layer[l - 1], t).hn, ci, ci, s->wx[l], s->wx_q[l], 3 * d.hidden,
+                                    const_cast<char*>(fwd_step(d, t).gx));
+                    mem[n++].d.bias = s->bx[l];
                 }
-            const int rc = run_group(s, kind, mem, epi, n, stream, dry, ws_need, false);
-            if (rc) return rc;
+            record_group(sc, s, kind, mem, n);
         }
-    }
-    return dry ? DVD_OK : launch_status();
 }
 
-int stack_backward(const dvd_gru_stack_desc* s, void* stream, bool dry, long long& ws_need) {
-    const int L = s->n_layers, T = s->layer[0].T, kind_ = stack_kind(s);
-    const long long M = (long long)s->layer[0].B * s->layer[0].H * s->layer[0].W;
-    const size_t esz = 2;
-    using T_ = bf16_t;
+void record_backward(const dvd_gru_stack_desc* s, Schedule& sc) {
+    const int L = s->n_layers, T = s->layer[0].T, kind = stack_kind(s);
     const int dx_in_a = s->layer[0].H == 8 ? 4 : 0;       // bit l: layer l's x-part backward-data rides in the NEXT pair's A group (see x_in_u)
-    if (!dry)
-        for (int l = 0; l < L; ++l)
-            if (hipMemsetAsync(s->layer[l].carry, 0, (size_t)M * s->layer[l].hidden * sizeof(float), S_) != hipSuccess) return DVD_E_LAUNCH;
-    // gradient wrt layer l's state of step t: from outside the stack (top layer) or from the x-path of the layer above
-    auto dh_of = [&](int l, int t) -> const char* {
-        const size_t step = (size_t)M * s->layer[l].hidden * esz;
-        if (l == L - 1) return s->layer[l].dh_out ? (const char*)s->layer[l].dh_out + t * step : nullptr;
-        return (const char*)s->dh_mid[l + 1] + t * step;
+    sc.backward = true;
+    // x-part backward-data convolution of (layer l >= 1, step t): the gradient reaching layer l-1's state of that step
+    auto dx_member = [&](int l, int t) {
+        const dvd_gru_desc& d = s->layer[l];
+        const int ci = s->cin[l], h = d.hidden;
+        const size_t off = (size_t)t * d.B * d.H * d.W * ci * 2;
+        Member m = member(d, kind, bwd_step(d, t, nullptr).dg, 3 * h, 3 * h, s->wdx[l], s->wdx_q[l], ci, (char*)s->dh_mid[l] + off);
+        if (s->layer[l - 1].dh_out) { m.d.res = (const char*)s->layer[l - 1].dh_out + off; m.d.ldres = ci; }
+        return m;
     };
-    for (int k = 0; k < T + 2 * (L - 1); ++k) {
-        Member mem[kMaxMember];
-        GruEpi epi[kMaxMember];
+    for (int k = 0; k < T + 2 * (L - 1); ++k)
         for (int phase = 0; phase < 2; ++phase) {                 // 0 = A group, 1 = B group
+            Member mem[kMaxMember];
             int n = 0;
-#ifndef DVD_A_GROUP_KIND                  // experiment: 1 = the A group of the >= 16-pixel stages on 128-row tiles (three workgroups per CU)
-#define DVD_A_GROUP_KIND 0
-#endif
-            const int kind = (phase == 0 && kind_ == 0 && DVD_A_GROUP_KIND) ? 1 : kind_;
             for (int l = L - 1; l >= 0; --l) {
                 const dvd_gru_desc& d = s->layer[l];
                 const int t = T - 1 - (k - 2 * (L - 1 - l)), h = d.hidden;
-                if (phase == 0 && l > 0 && ((dx_in_a >> l) & 1) && t >= -1 && t + 1 < T) {     // x-part backward-data of the step finished in the previous pair
-                    const int ci = s->cin[l];
-                    char* dgp = (char*)d.dg + (size_t)(t + 1) * M * 3 * h * esz;
-                    epi[n] = GruEpi{};
-                    member_conv(mem[n], d, dgp, 3 * h, 3 * h, s->wdx[l], s->wdx_q[l], ci, kind);
-                    mem[n].d.out = (char*)s->dh_mid[l] + (size_t)(t + 1) * M * ci * esz;
-                    mem[n].d.ldo = ci;
-                    if (s->layer[l - 1].dh_out) {
-                        mem[n].d.res = (const char*)s->layer[l - 1].dh_out + (size_t)(t + 1) * M * ci * esz;
-                        mem[n].d.ldres = ci;
-                    }
-                    ++n;
-                }
+                if (phase == 0 && l > 0 && ((dx_in_a >> l) & 1) && t >= -1 && t + 1 < T) mem[n++] = dx_member(l, t + 1);     // of the step finished in the previous pair
                 if (t < 0 || t >= T) continue;
-                const size_t step = (size_t)M * h * esz;
-                const char* hprev = t > 0 ? (const char*)d.h_all + (t - 1) * step : (const char*)d.h0;
-                const char* u = (const char*)d.u_all + t * step; const char* r = (const char*)d.r_all + t * step;
-                const char* o = (const char*)d.o_all + t * step;
-                char* dg = (char*)d.dg + (size_t)t * M * 3 * h * esz;
-                const unsigned grid = cdiv(M * (h / 8), 256);
+                const BwdStep st = bwd_step(d, t, stack_dh(s, l));
                 const bool has_prev = t > 0 || d.h0 != nullptr;
                 if (phase == 0) {
-                    if (t == T - 1 && !dry)                       // first BPTT step of the layer: nothing upstream to ride on
-                        gru_bwd_out_kernel<T_><<<grid, 256, 0, S_>>>((const T_*)dh_of(l, t), d.carry, nullptr, 0, (const T_*)u, (const T_*)o,
-                                                                     (const T_*)hprev, (T_*)dg, 3 * h, M, h);
-                    if (!has_prev) {
-                        if (!dry) gru_bwd_r_kernel<T_><<<grid, 256, 0, S_>>>(d.carry, nullptr, 0, (const T_*)r, (const T_*)nullptr, (T_*)dg, 3 * h, M, h);
-                        continue;
-                    }
-                    GruEpi& g = epi[n];
-                    g = GruEpi{};
-                    g.mode = 3; g.h = h; g.ldg = 3 * h; g.r = const_cast<char*>(r); g.hprev = hprev; g.h32n = d.carry; g.o = dg;
-                    member_conv(mem[n], d, dg + (size_t)2 * h * esz, h, 3 * h, d.wd_o, d.wd_o_q, h, kind);
-                    mem[n].d.out = d.carry; mem[n].gate = 1;
-                    ++n;
+                    if (t == T - 1) record_gate(sc, GK_BWD_OUT, l, t);      // first BPTT step of the layer: nothing upstream to ride on
+                    if (has_prev) mem[n++] = member(d, kind, st.dg + (size_t)2 * h * 2, h, 3 * h, d.wd_o, d.wd_o_q, h, d.carry, epi_bwd_r(d, st));
+                    else record_gate(sc, GK_BWD_R, l, t);
                 } else {
-                    if (has_prev) {
-                        GruEpi& g = epi[n];
-                        g = GruEpi{};
-                        g.h = h; g.ldg = 3 * h; g.h32n = d.carry;
-                        g.mode = 4;
-                        if (t > 0) {                              // ... and the first half of step t - 1
-                            const size_t tp = (size_t)(t - 1);
-                            g.mode = 5;
-                            g.gx = dh_of(l, t - 1);
-                            g.u_in = (const char*)d.u_all + tp * step;
-                            g.hr = const_cast<char*>((const char*)d.o_all + tp * step);
-                            g.hprev = t - 1 > 0 ? (const char*)d.h_all + (tp - 1) * step : (const char*)d.h0;
-                            g.o = (char*)d.dg + tp * M * 3 * h * esz;
-                        }
-                        member_conv(mem[n], d, dg, 2 * h, 3 * h, d.wd_ur, d.wd_ur_q, h, kind);
-                        mem[n].d.out = d.carry; mem[n].gate = 1;
-                        ++n;
-                    }
-                    if (l > 0 && !((dx_in_a >> l) & 1)) {         // x-part backward-data: gradient reaching layer l-1's state of step t
-                        const int ci = s->cin[l];
-                        epi[n] = GruEpi{};
-                        member_conv(mem[n], d, dg, 3 * h, 3 * h, s->wdx[l], s->wdx_q[l], ci, kind);
-                        mem[n].d.out = (char*)s->dh_mid[l] + (size_t)t * M * ci * esz;
-                        mem[n].d.ldo = ci;
-                        if (s->layer[l - 1].dh_out) {
-                            mem[n].d.res = (const char*)s->layer[l - 1].dh_out + (size_t)t * M * ci * esz;
-                            mem[n].d.ldres = ci;
-                        }
-                        ++n;
-                    }
+                    if (has_prev)                                 // ... and the first half of step t - 1
+                        mem[n++] = member(d, kind, st.dg, 2 * h, 3 * h, d.wd_ur, d.wd_ur_q, h, d.carry, epi_bwd_ur(d, t, stack_dh(s, l)));
+                    if (l > 0 && !((dx_in_a >> l) & 1)) mem[n++] = dx_member(l, t);
                 }
             }
-            const int rc = run_group(s, kind, mem, epi, n, stream, dry, ws_need, true);
-            if (rc) return rc;
+            record_group(sc, s, kind, mem, n);
+        }
+    for (int l = 0; l < L; ++l)
+        if (s->layer[l].dh0) record_gate(sc, GK_DH0, l, 0);
+}
+
+void record(const dvd_gru_stack_desc* s, bool backward, Schedule& sc) {
+    const size_t groups = 2 * (size_t)(s->layer[0].T + 2 * (s->n_layers - 1));
+    sc.ops.reserve(groups + 3 * s->n_layers);
+    sc.d.reserve(groups * (2 * s->n_layers - 1));
+    sc.g.reserve(groups * (2 * s->n_layers - 1));
+    if (backward) record_backward(s, sc); else record_forward(s, sc);
+}
+
+// Argument and shape rules, then the schedule itself: a stack is served only if no grouped launch of it needs more than kGroupMax members
+int stack_check(const dvd_gru_stack_desc* s, bool backward, Schedule& sc) {
+    if (!s || s->n_layers < 1 || s->n_layers > DVD_GRU_STACK_MAX) return DVD_E_ARG;
+    const dvd_gru_desc& a = s->layer[0];
+    if (a.dtype != DVD_BF16 || a.T <= 0 || a.B <= 0 || !a.tickets || !s->ws) return DVD_E_ARG;
+    if (stack_kind(s) < 0) return DVD_E_SHAPE;
+    for (int l = 0; l < s->n_layers; ++l) {
+        const dvd_gru_desc& d = s->layer[l];
+        if (d.dtype != a.dtype || d.T != a.T || d.B != a.B || d.H != a.H || d.W != a.W) return DVD_E_ARG;
+        if (d.hidden <= 0 || (d.hidden & 7) || (d.k != 3 && d.k != 5)) return DVD_E_SHAPE;
+        if ((long long)d.B * d.H * d.W * (d.hidden / 8) >= (1ll << 31)) return DVD_E_SHAPE;
+        if (!d.gx || !d.h_all || !d.u_all || !d.hr_all) return DVD_E_ARG;
+        if (l > 0 && (s->cin[l] != s->layer[l - 1].hidden || d.gx_stride != (long long)d.B * d.H * d.W * 3 * d.hidden)) return DVD_E_ARG;
+        if (!backward) {
+            if (!d.w_ur || !d.w_o || !d.w_ur_q || !d.w_o_q) return DVD_E_ARG;
+            if (!d.infer && (!d.r_all || !d.o_all)) return DVD_E_ARG;
+            if (l > 0 && (!s->wx[l] || !s->wx_q[l] || !s->bx[l])) return DVD_E_ARG;
+        } else {
+            if (!d.wd_ur || !d.wd_o || !d.wd_ur_q || !d.wd_o_q || !d.r_all || !d.o_all || !d.dg || !d.carry) return DVD_E_ARG;
+            if (l > 0 && (!s->wdx[l] || !s->wdx_q[l] || !s->dh_mid[l])) return DVD_E_ARG;
         }
     }
-    if (!dry)
-        for (int l = 0; l < L; ++l) {
+    record(s, backward, sc);
+    return sc.max_members > kGroupMax ? DVD_E_SHAPE : DVD_OK;
+}
+
+// Issues a recorded pass on `stream`
+int play(const dvd_gru_stack_desc* s, const Schedule& sc, void* stream) {
+    if (sc.backward)
+        for (int l = 0; l < s->n_layers; ++l) {
             const dvd_gru_desc& d = s->layer[l];
-            if (d.dh0) gru_dh0_kernel<<<cdiv(M * d.hidden, 256), 256, 0, S_>>>(d.carry, nullptr, 0, d.dh0, M, d.hidden);
+            if (hipMemsetAsync(d.carry, 0, (size_t)d.B * d.H * d.W * d.hidden * sizeof(float), S_) != hipSuccess) return DVD_E_LAUNCH;
         }
-    return dry ? DVD_OK : launch_status();
+    for (const Launch& op : sc.ops) {
+        int rc;
+        if (op.kind < 0) rc = gate_kernel(op.which, s->layer[op.layer], op.t, stack_dh(s, op.layer), nullptr, 0, stream);
+        else {
+            for (long long seen = g_ws_high.load(); op.ws_end > seen && !g_ws_high.compare_exchange_weak(seen, op.ws_end);) {}
+            rc = dvd_conv_forward_group(&sc.d[op.first], &sc.g[op.first], op.n, op.kind, s->run, stream);
+        }
+        if (rc) return rc;
+    }
+    return launch_status();
 }
 
 }  // namespace
@@ -827,14 +761,16 @@ extern "C" int dvd_convgru_stack_ok(const dvd_gru_stack_desc* d, int backward) {
     t = *d;
     static float dummy;
     if (!t.ws) t.ws = &dummy;                                     // (a geometry / pointer-completeness query: the workspace may not exist yet)
-    return stack_check(&t, backward != 0) == DVD_OK ? 1 : 0;
+    Schedule sc;
+    return stack_check(&t, backward != 0, sc) == DVD_OK ? 1 : 0;
 }
 extern "C" long long dvd_convgru_stack_ws_floats(const dvd_gru_stack_desc* d) {
     if (!d || d->n_layers < 1 || d->n_layers > DVD_GRU_STACK_MAX || stack_kind(d) < 0) return 0;
-    long long need = 0, nb = 0;
-    stack_forward(d, nullptr, true, need);
-    stack_backward(d, nullptr, true, nb);
-    if (nb > need) need = nb;
+    Schedule f, b;
+    record(d, false, f);
+    record(d, true, b);
+    if (std::max(f.max_members, b.max_members) > kGroupMax) return 0;
+    const long long need = std::max(f.ws_floats, b.ws_floats);
     g_ws_sized.store(need);
     return need > 0 ? need : 1;
 }
@@ -845,14 +781,35 @@ extern "C" void dvd_debug_stack_ws(long long* out, int reset) {
     if (reset) g_ws_high.store(0);
 }
 extern "C" int dvd_convgru_stack_forward(const dvd_gru_stack_desc* d, void* stream) {
-    const int rc = stack_check(d, false);
-    if (rc) return rc;
-    long long need = dvd_convgru_stack_ws_floats(d);      // what the caller was told to allocate: the launch refuses to go past it
-    return stack_forward(d, stream, false, need);
+    Schedule sc;
+    const int rc = stack_check(d, false, sc);
+    return rc ? rc : play(d, sc, stream);
 }
 extern "C" int dvd_convgru_stack_backward(const dvd_gru_stack_desc* d, void* stream) {
-    const int rc = stack_check(d, true);
-    if (rc) return rc;
-    long long need = dvd_convgru_stack_ws_floats(d);
-    return stack_backward(d, stream, false, need);
+    Schedule sc;
+    const int rc = stack_check(d, true, sc);
+    return rc ? rc : play(d, sc, stream);
+}
+
+// Test hook (tests/native/stack_schedule.cpp; hidden from the library's exports): the recorded schedule of one pass as text, one line
+// per launch in issue order.  Only the geometry is looked at: the pointers of `d` may be placeholders.
+extern "C" int dvd_convgru_stack_dump(const dvd_gru_stack_desc* d, int backward, FILE* out) {
+    if (!d || d->n_layers < 1 || d->n_layers > DVD_GRU_STACK_MAX || stack_kind(d) < 0) return DVD_E_SHAPE;
+    Schedule sc;
+    record(d, backward != 0, sc);
+    for (const Launch& op : sc.ops) {
+        if (op.kind < 0) {
+            fprintf(out, "%s h=%d t=%d\n", kGateKernelName[op.which], d->layer[op.layer].hidden, op.t);
+            continue;
+        }
+        fprintf(out, "%s kind=%d", backward ? "bwd" : "fwd", op.kind);
+        for (int i = op.first; i < op.first + op.n; ++i) {
+            const dvd_conv_desc& c = sc.d[i];
+            fprintf(out, " | C=%d ldi=%d Cout=%d k=%d mode=%d bias=%d res=%d ns=%d off=%lld", c.C, c.ldi, c.Cout, c.kh, sc.g[i].mode,
+                    c.bias != nullptr, c.res != nullptr, c.nsplit, c.nsplit > 1 ? (long long)(sc.g[i].slabs - d->ws) : -1ll);
+        }
+        fprintf(out, "\n");
+    }
+    fprintf(out, "ws=%lld max_members=%d\n", sc.ws_floats, sc.max_members);
+    return DVD_OK;
 }

@@ -418,6 +418,76 @@ GRU_NS_CAP = 0               # dvd_gru_desc.ns_cap (tests: a common upper bound 
 GRU_COMBINE_MAX = 0          # dvd_gru_desc.combine_max: 0 = the library's default policy (tests raise it to cover every slice count)
 
 
+def _gru_packs(wu, wr, wo, dtype, dev, pb=None):
+    """The three packs of a layer -- x-part of all gates, recurrent [u|r], recurrent out gate -- filled directly or, with `pb`
+    (K.PackBatch), queued for its one launch."""
+    hid, ctot, k = wu.shape[0], wu.shape[1], wu.shape[-1]
+    cin = ctot - hid
+    px = K.PackedConv(dtype, 3 * hid, cin, (k, k), dev, covered=True)     # the fills below write every output channel
+    pur = K.PackedConv(dtype, 2 * hid, hid, (k, k), dev, covered=True)
+    po = K.PackedConv(dtype, hid, hid, (k, k), dev, covered=True)
+    fill = pb.fill if pb is not None else (lambda pk, w, **kw: pk.fill(w, **kw))
+    for g, w in enumerate((wu, wr, wo)):
+        fill(px, w, co_off=g * hid, ci_off=0)
+    fill(pur, wu, co_off=0, ci_off=cin)
+    fill(pur, wr, co_off=hid, ci_off=cin)
+    fill(po, wo, ci_off=cin)
+    return px, pur, po
+
+
+def _gru_states(x, T, B, hid, infer):
+    """(h, u, r, o, h*r), each [T,B,S,S,hid].  infer: u and h*r are one-step scratch buffers, r and o are not stored at all."""
+    mk = lambda n=T: torch.empty(n, B, x.shape[1], x.shape[2], hid, dtype=x.dtype, device=x.device)
+    if infer:
+        return mk(), mk(1), None, None, mk(1)
+    return mk(), mk(), mk(), mk(), mk()
+
+
+def _gru_desc(d, x, T, B, hid, k, states, h0):
+    """What the forward and the backward filling of a GruDesc share: geometry, states, initial state, tickets, test knobs."""
+    d.dtype, d.T, d.B, d.H, d.W, d.hidden, d.k = L.dt(x), T, B, x.shape[1], x.shape[2], hid, k
+    d.h0 = h0.data_ptr() if h0 is not None else None
+    for name, t in zip(("h_all", "u_all", "r_all", "o_all", "hr_all"), states):
+        setattr(d, name, t.data_ptr() if t is not None else None)
+    d.tickets = L.gru_tickets(x.device).data_ptr()
+    d.combine_max = GRU_COMBINE_MAX
+    d.ns_cap = GRU_NS_CAP
+
+
+def _gru_desc_forward(d, x, T, B, hid, k, states, h0, gx, gx_stride, pur, po, h32, infer):
+    _gru_desc(d, x, T, B, hid, k, states, h0)
+    d.gx_stride = gx_stride
+    d.gx, d.w_ur, d.w_o = gx.data_ptr(), pur.wf.data_ptr(), po.wf.data_ptr()
+    d.h32 = h32.data_ptr() if h32 is not None else None
+    d.infer = int(infer)
+
+
+def _gru_desc_backward(d, x, T, B, hid, k, states, h0, pur, po, dh, dg, carry, want_dh0):
+    """Returns the fp32 buffer of the gradient wrt h0 (ConvGRU.py:104), or None."""
+    _gru_desc(d, x, T, B, hid, k, states, h0)
+    d.wd_ur, d.wd_o = pur.wd.data_ptr(), po.wd.data_ptr()
+    d.dh_out = dh.data_ptr() if dh is not None else None
+    d.dg, d.carry = dg.data_ptr(), carry.data_ptr()
+    if h0 is None or not want_dh0:
+        return None
+    dh0_32 = torch.empty(B * x.shape[1] * x.shape[2], hid, dtype=torch.float32, device=x.device)
+    d.dh0 = dh0_32.data_ptr()
+    return dh0_32
+
+
+def _gru_dx(dg, px, k, T, B, hid, shared_x, need_dx):
+    """Layer 0: (dgx, dx) -- d(pre-activation) as the x-part sees it (summed over T for a shared input) and the input gradient."""
+    dgx = K.sum_leading(dg.view(T, -1)).view(B, dg.shape[1], dg.shape[2], 3 * hid) if shared_x else dg
+    dx = K.conv_forward(dgx, px.wd, (k, k), px.cip, wq=lambda: px.fragment_major("wd")) if need_dx else None
+    return dgx, dx
+
+
+def _gru_dh0(dh0_32, h0):
+    if dh0_32 is None:
+        return None
+    return dh0_32.view(h0.shape) if h0.dtype == torch.float32 else K.convert(dh0_32, h0.dtype).view(h0.shape)
+
+
 class ConvGRULayer(Function):
     """All T steps of one ConvGRUCell (ConvGRU.py:29-54).  x: [T*B,S,S,Cin_p] t-major frames, or
     [B,S,S,Cin_p] when the same input feeds every step (first GRU of the generator).
@@ -434,53 +504,28 @@ class ConvGRULayer(Function):
         B = x.shape[0] if shared_x else x.shape[0] // T
         S1, S2 = x.shape[1], x.shape[2]
         M = B * S1 * S2
-        px = K.PackedConv(dtype, 3 * hid, cin, (k, k), dev, covered=True)     # the fills below write every output channel
-        pur = K.PackedConv(dtype, 2 * hid, hid, (k, k), dev, covered=True)
-        po = K.PackedConv(dtype, hid, hid, (k, k), dev, covered=True)
-        for g, w in enumerate((wu, wr, wo)):
-            px.fill(w, co_off=g * hid, ci_off=0)
-        pur.fill(wu, co_off=0, ci_off=cin).fill(wr, co_off=hid, ci_off=cin)
-        po.fill(wo, ci_off=cin)
+        px, pur, po = _gru_packs(wu, wr, wo, dtype, dev)
         bias3 = torch.cat([bu, br, bo])
         gx = K.conv_forward(x, px.wf, (k, k), 3 * hid, bias=bias3, wq=lambda: px.fragment_major("wf"))
-        mk = lambda n=T: torch.empty(n, B, S1, S2, hid, dtype=dtype, device=dev)
-        if infer:
-            h_all, u_all, hr_all, r_all, o_all = mk(), mk(1), mk(1), None, None
-        else:
-            h_all, u_all, r_all, o_all, hr_all = mk(), mk(), mk(), mk(), mk()
+        states = _gru_states(x, T, B, hid, infer)
         h32 = torch.empty(2, M, hid, dtype=torch.float32, device=dev) if dtype != torch.float32 else None
         lib = L.lib()
-        ntaps = k * k
-        ns1 = lib.dvd_conv_pick_nsplit(L.dt(x), C.c_longlong(M), 2 * hid, hid, ntaps)
-        ns2 = lib.dvd_conv_pick_nsplit(L.dt(x), C.c_longlong(M), hid, hid, ntaps)
-        ns3 = lib.dvd_conv_pick_nsplit(L.dt(x), C.c_longlong(M), hid, 2 * hid, ntaps)
-        if GRU_NS_CAP > 0:
-            ns1, ns2, ns3 = min(ns1, GRU_NS_CAP), min(ns2, GRU_NS_CAP), min(ns3, GRU_NS_CAP)
+        nsplit = lambda cout, c: min(lib.dvd_conv_pick_nsplit(L.dt(x), C.c_longlong(M), cout, c, k * k), GRU_NS_CAP or 1 << 30)
         ws_n = lib.dvd_convgru_ws_floats(L.dt(x), B, S1, S2, hid, k)
         ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
         d = L.GruDesc()
-        d.dtype, d.T, d.B, d.H, d.W, d.hidden, d.k = L.dt(x), T, B, S1, S2, hid, k
-        d.gx_stride = 0 if shared_x else M * 3 * hid
-        d.gx, d.w_ur, d.w_o = gx.data_ptr(), pur.wf.data_ptr(), po.wf.data_ptr()
+        _gru_desc_forward(d, x, T, B, hid, k, states, h0, gx, 0 if shared_x else M * 3 * hid, pur, po, h32, infer)
         # the recurrent convolutions on frames of 16 pixels and more read their weights in fragment-major order
-        if K.wants_fragment_major(dtype, B, S1, S2, hid, 2 * hid, k, ns1):
+        if K.wants_fragment_major(dtype, B, S1, S2, hid, 2 * hid, k, nsplit(2 * hid, hid)):
             d.w_ur_q = pur.fragment_major("wf").data_ptr()
-        if K.wants_fragment_major(dtype, B, S1, S2, hid, hid, k, ns2):
+        if K.wants_fragment_major(dtype, B, S1, S2, hid, hid, k, nsplit(hid, hid)):
             d.w_o_q = po.fragment_major("wf").data_ptr()
-        d.h0 = h0.data_ptr() if h0 is not None else None
-        d.h_all, d.u_all, d.hr_all = h_all.data_ptr(), u_all.data_ptr(), hr_all.data_ptr()
-        d.r_all = r_all.data_ptr() if r_all is not None else None
-        d.o_all = o_all.data_ptr() if o_all is not None else None
-        d.h32 = h32.data_ptr() if h32 is not None else None
         d.ws = ws.data_ptr()
-        d.tickets = L.gru_tickets(dev).data_ptr()
-        d.combine_max = GRU_COMBINE_MAX
-        d.ns_cap = GRU_NS_CAP
-        d.infer = int(infer)
         L.check(lib.dvd_convgru_layer_forward(C.byref(d), L.stream()))
+        h_all = states[0]
         if infer:
             return h_all.view(T * B, S1, S2, hid)
-        ctx.save_for_backward(x, wu, wr, wo, h_all, u_all, r_all, o_all, hr_all, h0)
+        ctx.save_for_backward(x, wu, wr, wo, *states, h0)
         ctx.params = (wu, bu, wr, br, wo, bo)
         ctx.packs = (px, pur, po)
         ctx.meta = (T, B, S1, S2, hid, cin, k, shared_x, ws_n)
@@ -497,38 +542,21 @@ class ConvGRULayer(Function):
         dg = torch.empty(T * B, S1, S2, 3 * hid, dtype=dtype, device=dev)
         carry = torch.empty(M, hid, dtype=torch.float32, device=dev)
         ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
-        d = L.GruDesc()
-        d.dtype, d.T, d.B, d.H, d.W, d.hidden, d.k = L.dt(x), T, B, S1, S2, hid, k
-        d.wd_ur, d.wd_o = pur.wd.data_ptr(), po.wd.data_ptr()
         lib = L.lib()
-        ns_o = lib.dvd_conv_pick_nsplit(L.dt(x), C.c_longlong(M), hid, hid, k * k)
-        ns_ur = lib.dvd_conv_pick_nsplit(L.dt(x), C.c_longlong(M), hid, 2 * hid, k * k)
-        if GRU_NS_CAP > 0:
-            ns_o, ns_ur = min(ns_o, GRU_NS_CAP), min(ns_ur, GRU_NS_CAP)
-        if K.wants_fragment_major(dtype, B, S1, S2, 2 * hid, hid, k, ns_ur):
+        nsplit = lambda cout, c: min(lib.dvd_conv_pick_nsplit(L.dt(x), C.c_longlong(M), cout, c, k * k), GRU_NS_CAP or 1 << 30)
+        d = L.GruDesc()
+        dh0_32 = _gru_desc_backward(d, x, T, B, hid, k, (h_all, u_all, r_all, o_all, hr_all), h0, pur, po, dh, dg, carry,
+                                    ctx.needs_input_grad[9])
+        if K.wants_fragment_major(dtype, B, S1, S2, 2 * hid, hid, k, nsplit(hid, 2 * hid)):
             d.wd_ur_q = pur.fragment_major("wd").data_ptr()
-        if K.wants_fragment_major(dtype, B, S1, S2, hid, hid, k, ns_o):
+        if K.wants_fragment_major(dtype, B, S1, S2, hid, hid, k, nsplit(hid, hid)):
             d.wd_o_q = po.fragment_major("wd").data_ptr()
-        d.h0 = h0.data_ptr() if h0 is not None else None
-        d.h_all, d.u_all, d.r_all = h_all.data_ptr(), u_all.data_ptr(), r_all.data_ptr()
-        d.o_all, d.hr_all = o_all.data_ptr(), hr_all.data_ptr()
-        d.ws, d.dh_out, d.dg, d.carry = ws.data_ptr(), dh.data_ptr(), dg.data_ptr(), carry.data_ptr()
-        d.tickets = L.gru_tickets(dev).data_ptr()
-        d.combine_max = GRU_COMBINE_MAX
-        d.ns_cap = GRU_NS_CAP
-        dh0_32 = None
-        if h0 is not None and ctx.needs_input_grad[9]:          # gradient wrt the supplied initial state (ConvGRU.py:104)
-            dh0_32 = torch.empty(M, hid, dtype=torch.float32, device=dev)
-            d.dh0 = dh0_32.data_ptr()
-        L.check(L.lib().dvd_convgru_layer_backward(C.byref(d), L.stream()))
+        d.ws = ws.data_ptr()
+        L.check(lib.dvd_convgru_layer_backward(C.byref(d), L.stream()))
         # ---- everything below is batched over all T steps ----
-        dgx = K.sum_leading(dg.view(T, -1)).view(B, S1, S2, 3 * hid) if shared_x else dg
-        dx = K.conv_forward(dgx, px.wd, (k, k), px.cip, wq=lambda: px.fragment_major("wd")) if ctx.needs_input_grad[0] else None
+        dgx, dx = _gru_dx(dg, px, k, T, B, hid, shared_x, ctx.needs_input_grad[0])
         grads, dbl = _gru_gate_wgrads(x, dgx, dg, h_all, hr_all, h0, ctx.params, (T, B, S1, S2, hid, cin, k), (wu, wr, wo))
-        dh0 = None
-        if dh0_32 is not None:
-            dh0 = dh0_32.view(h0.shape) if h0.dtype == torch.float32 else K.convert(dh0_32, h0.dtype).view(h0.shape)
-        return (dx, grads[0], dbl[0], grads[1], dbl[1], grads[2], dbl[2], None, None, dh0, None)
+        return (dx, grads[0], dbl[0], grads[1], dbl[1], grads[2], dbl[2], None, None, _gru_dh0(dh0_32, h0), None)
 
 
 class ConvGRUStack(Function):
@@ -538,14 +566,33 @@ class ConvGRUStack(Function):
     (or None).  Returns the per-layer state sequences [T*B,S,S,h_l].  Same results as ConvGRULayer applied layer by layer."""
 
     @staticmethod
-    def usable(x, cells):
-        """Host-side pre-check (the library's dvd_convgru_stack_ok has the last word inside forward)."""
+    def usable(x, cells, T=None, shared_x=False, hidden=None):
+        """Whether the library serves this ConvGRU as a wavefront, forward and backward.  Python knows the switch, the dtype and
+        the descriptor's capacity; every shape rule is the library's (dvd_convgru_stack_ok on a geometry-only descriptor: its
+        answer comes from the schedule it would record -- placeholder pointers, nothing is launched or dereferenced).
+        T = None asks for sequences of ANY length: the schedule of one just long enough to fill the pipeline, which holds the
+        largest groups a longer one can have."""
         if x.dtype != torch.bfloat16 or not GRU_STACK or len(cells) > L.GRU_STACK_MAX:
             return False
-        S1, S2 = x.shape[1], x.shape[2]
-        if S1 != S2 or S1 & (S1 - 1) or not (S1 in (4, 8) or S1 >= 16):
-            return False
-        return all(c.kernel_size in (3, 5) and c.hidden_size % 8 == 0 for c in cells)
+        if T is None:
+            T, shared_x = 2 * len(cells) + 1, True
+        B = max(1, x.shape[0] if shared_x else x.shape[0] // T)      # (B sizes the tiles, not the schedule: any x with the frame size will do)
+        sd = L.GruStackDesc()
+        sd.n_layers, sd.layer_policy, sd.ws = len(cells), GRU_STACK_LAYER_POLICY, 1
+        for l, c in enumerate(cells):
+            d = sd.layer[l]
+            d.dtype, d.T, d.B, d.H, d.W, d.hidden, d.k = L.BF16, T, B, x.shape[1], x.shape[2], c.hidden_size, c.kernel_size
+            d.gx_stride, d.ns_cap = B * x.shape[1] * x.shape[2] * 3 * c.hidden_size, GRU_NS_CAP
+            for f in ("gx", "w_ur", "w_o", "w_ur_q", "w_o_q", "wd_ur", "wd_o", "wd_ur_q", "wd_o_q", "h_all", "u_all", "r_all", "o_all",
+                      "hr_all", "tickets", "dg", "carry"):
+                setattr(d, f, 1)
+            if hidden is not None and hidden[l] is not None:
+                d.h0 = 1                                 # (a supplied state puts the layer's step 0 into the grouped launches)
+            if l:
+                sd.cin[l] = cells[l - 1].hidden_size
+                sd.wx[l] = sd.wx_q[l] = sd.bx[l] = sd.wdx[l] = sd.wdx_q[l] = sd.dh_mid[l] = 1
+        lib = L.lib()
+        return bool(lib.dvd_convgru_stack_ok(C.byref(sd), 0) and lib.dvd_convgru_stack_ok(C.byref(sd), 1))
 
     @staticmethod
     def forward(ctx, x, T, shared_x, infer, nl, *flat):
@@ -559,25 +606,15 @@ class ConvGRUStack(Function):
         sd = L.GruStackDesc()
         sd.n_layers, sd.layer_policy, sd.run = nl, GRU_STACK_LAYER_POLICY, 0
         keep, layers = [], []
-        inp = x
         # the 6 gate packs of every layer and their fragment-major images (the backward pass's too unless `infer`) in TWO launches for
         # the whole ConvGRU (K.PackBatch) instead of 12-15 per layer, all of them in front of the first convolution
         pb, packs = K.PackBatch(), []
         for l, (wu, bu, wr, br, wo, bo) in enumerate(wts):
-            hid, ctot, k = wu.shape[0], wu.shape[1], wu.shape[-1]
-            cin = ctot - hid
-            px = K.PackedConv(dtype, 3 * hid, cin, (k, k), dev, covered=True)
-            pur = K.PackedConv(dtype, 2 * hid, hid, (k, k), dev, covered=True)
-            po = K.PackedConv(dtype, hid, hid, (k, k), dev, covered=True)
-            for g, w in enumerate((wu, wr, wo)):
-                pb.fill(px, w, co_off=g * hid, ci_off=0)
-            pb.fill(pur, wu, co_off=0, ci_off=cin).fill(pur, wr, co_off=hid, ci_off=cin)
-            pb.fill(po, wo, ci_off=cin)
-            for pk in (px, pur, po):
+            packs.append(_gru_packs(wu, wr, wo, dtype, dev, pb))
+            for pk in packs[l]:
                 pb.fragment_major(pk, "wf")
-                if not infer and (pk is not px or l > 0 or ctx.needs_input_grad[0]):
+                if not infer and (pk is not packs[l][0] or l > 0 or ctx.needs_input_grad[0]):
                     pb.fragment_major(pk, "wd")
-            packs.append((px, pur, po))
         pb.run()
         for l, (wu, bu, wr, br, wo, bo) in enumerate(wts):
             hid, ctot, k = wu.shape[0], wu.shape[1], wu.shape[-1]
@@ -590,45 +627,27 @@ class ConvGRUStack(Function):
                 gx = torch.empty(T * B, S1, S2, 3 * hid, dtype=dtype, device=dev)
                 sd.cin[l] = K.pad8(cin)
                 sd.wx[l], sd.wx_q[l], sd.bx[l] = px.wf.data_ptr(), px.fragment_major("wf").data_ptr(), bias3.data_ptr()
-            mk = lambda n=T: torch.empty(n, B, S1, S2, hid, dtype=dtype, device=dev)
-            if infer:
-                h_all, u_all, hr_all, r_all, o_all = mk(), mk(1), mk(1), None, None
-            else:
-                h_all, u_all, r_all, o_all, hr_all = mk(), mk(), mk(), mk(), mk()
+            states = _gru_states(x, T, B, hid, infer)
             h32 = torch.empty(2, M, hid, dtype=torch.float32, device=dev)
-            h0 = h0s[l]
             d = sd.layer[l]
-            d.dtype, d.T, d.B, d.H, d.W, d.hidden, d.k = L.dt(x), T, B, S1, S2, hid, k
-            d.gx_stride = 0 if (shared_x and l == 0) else M * 3 * hid
-            d.gx, d.w_ur, d.w_o = gx.data_ptr(), pur.wf.data_ptr(), po.wf.data_ptr()
+            _gru_desc_forward(d, x, T, B, hid, k, states, h0s[l], gx, 0 if (shared_x and l == 0) else M * 3 * hid, pur, po, h32, infer)
             d.w_ur_q, d.w_o_q = pur.fragment_major("wf").data_ptr(), po.fragment_major("wf").data_ptr()
-            d.h0 = h0.data_ptr() if h0 is not None else None
-            d.h_all, d.u_all, d.hr_all = h_all.data_ptr(), u_all.data_ptr(), hr_all.data_ptr()
-            d.r_all = r_all.data_ptr() if r_all is not None else None
-            d.o_all = o_all.data_ptr() if o_all is not None else None
-            d.h32 = h32.data_ptr()
-            d.tickets = L.gru_tickets(dev).data_ptr()
-            d.ns_cap = GRU_NS_CAP
-            d.infer = int(infer)
             keep.append((gx, h32, bias3))
-            layers.append(dict(px=px, pur=pur, po=po, h_all=h_all, u_all=u_all, r_all=r_all, o_all=o_all, hr_all=hr_all,
-                               hid=hid, cin=cin, k=k))
+            layers.append((states, hid, cin, k))
         ws = torch.empty(lib.dvd_convgru_stack_ws_floats(C.byref(sd)), dtype=torch.float32, device=dev)
         sd.ws = ws.data_ptr()
-        if not lib.dvd_convgru_stack_ok(C.byref(sd), 0):
-            raise RuntimeError("ConvGRUStack: this stack is not served by the wavefront path (ConvGRUStack.usable disagrees with the library)")
-        L.check(lib.dvd_convgru_stack_forward(C.byref(sd), L.stream()))
-        outs = tuple(ly["h_all"].view(T * B, S1, S2, ly["hid"]) for ly in layers)
+        L.check(lib.dvd_convgru_stack_forward(C.byref(sd), L.stream()))      # (refuses, before any launch, what `usable` would have refused)
+        outs = tuple(states[0].view(T * B, S1, S2, hid) for states, hid, _, _ in layers)
         if infer:
             return outs
         ctx.set_materialize_grads(False)          # unused layer outputs arrive as None, not as zero tensors
         saved = [x]
-        for l, ly in enumerate(layers):
-            saved += [wts[l][0], wts[l][2], wts[l][4], ly["h_all"], ly["u_all"], ly["r_all"], ly["o_all"], ly["hr_all"], h0s[l]]
+        for l, (states, _, _, _) in enumerate(layers):
+            saved += [wts[l][0], wts[l][2], wts[l][4], *states, h0s[l]]
         ctx.save_for_backward(*saved)
         ctx.params = [tuple(w) for w in wts]
-        ctx.packs = [(ly["px"], ly["pur"], ly["po"]) for ly in layers]
-        ctx.meta = (T, B, S1, S2, shared_x, nl, [(ly["hid"], ly["cin"], ly["k"]) for ly in layers])
+        ctx.packs = packs
+        ctx.meta = (T, B, S1, S2, shared_x, nl, [ly[1:] for ly in layers])
         return outs
 
     @staticmethod
@@ -644,34 +663,24 @@ class ConvGRUStack(Function):
         sd.n_layers, sd.layer_policy, sd.run = nl, GRU_STACK_LAYER_POLICY, 0
         dgs, carries, dh_mid, dh0_32, keep = [], [], [None] * nl, [None] * nl, []
         for l in range(nl):
-            wu, wr, wo, h_all, u_all, r_all, o_all, hr_all, h0 = per[l]
+            h0 = per[l][8]
             hid, cin, k = dims[l]
             px, pur, po = ctx.packs[l]
             dg = torch.empty(T * B, S1, S2, 3 * hid, dtype=dtype, device=dev)
             carry = torch.empty(M, hid, dtype=torch.float32, device=dev)
-            d = sd.layer[l]
-            d.dtype, d.T, d.B, d.H, d.W, d.hidden, d.k = L.dt(x), T, B, S1, S2, hid, k
-            d.gx_stride = M * 3 * hid
-            d.gx = dg.data_ptr()                         # (not read by the backward pass; the descriptor check wants it non-null)
-            d.wd_ur, d.wd_o = pur.wd.data_ptr(), po.wd.data_ptr()
-            d.wd_ur_q, d.wd_o_q = pur.fragment_major("wd").data_ptr(), po.fragment_major("wd").data_ptr()
-            d.h0 = h0.data_ptr() if h0 is not None else None
-            d.h_all, d.u_all, d.r_all = h_all.data_ptr(), u_all.data_ptr(), r_all.data_ptr()
-            d.o_all, d.hr_all = o_all.data_ptr(), hr_all.data_ptr()
-            d.dg, d.carry = dg.data_ptr(), carry.data_ptr()
             dh = dhs[l].contiguous() if dhs[l] is not None else None
-            d.dh_out = dh.data_ptr() if dh is not None else None
             keep.append(dh)
-            d.tickets = L.gru_tickets(dev).data_ptr()
-            d.ns_cap = GRU_NS_CAP
+            d = sd.layer[l]
             if l > 0:
                 sd.cin[l] = K.pad8(cin)
                 sd.wdx[l], sd.wdx_q[l] = px.wd.data_ptr(), px.fragment_major("wd").data_ptr()
                 dh_mid[l] = torch.empty(T * B, S1, S2, K.pad8(cin), dtype=dtype, device=dev)
                 sd.dh_mid[l] = dh_mid[l].data_ptr()
-            if h0 is not None and ctx.needs_input_grad[5 + 6 * nl + l]:
-                dh0_32[l] = torch.empty(M, hid, dtype=torch.float32, device=dev)
-                d.dh0 = dh0_32[l].data_ptr()
+            dh0_32[l] = _gru_desc_backward(d, x, T, B, hid, k, per[l][3:8], h0, pur, po, dh, dg, carry,
+                                           ctx.needs_input_grad[5 + 6 * nl + l])
+            d.gx_stride = M * 3 * hid
+            d.gx = dg.data_ptr()                         # (not read by the backward pass; the descriptor check wants it non-null)
+            d.wd_ur_q, d.wd_o_q = pur.fragment_major("wd").data_ptr(), po.fragment_major("wd").data_ptr()
             dgs.append(dg)
             carries.append(carry)
         ws = torch.empty(lib.dvd_convgru_stack_ws_floats(C.byref(sd)), dtype=torch.float32, device=dev)
@@ -683,12 +692,9 @@ class ConvGRUStack(Function):
         for l in range(nl):
             wu, wr, wo, h_all, u_all, r_all, o_all, hr_all, h0 = per[l]
             hid, cin, k = dims[l]
-            px = ctx.packs[l][0]
             dg = dgs[l]
             if l == 0:
-                dgx = K.sum_leading(dg.view(T, -1)).view(B, S1, S2, 3 * hid) if shared_x else dg
-                if ctx.needs_input_grad[0]:
-                    dx = K.conv_forward(dgx, px.wd, (k, k), px.cip, wq=lambda: px.fragment_major("wd"))
+                dgx, dx = _gru_dx(dg, ctx.packs[0][0], k, T, B, hid, shared_x, ctx.needs_input_grad[0])
                 xin = x
             else:
                 dgx = dg
@@ -699,14 +705,7 @@ class ConvGRUStack(Function):
             # through record_stream): release them layer by layer instead of keeping every layer's [T*B,S,S,3h] until the return
             dg = dgx = None
             dgs[l] = carries[l] = dh_mid[l] = None
-        dh0s = []
-        for l in range(nl):
-            h0 = per[l][8]
-            if dh0_32[l] is None:
-                dh0s.append(None)
-            else:
-                dh0s.append(dh0_32[l].view(h0.shape) if h0.dtype == torch.float32 else K.convert(dh0_32[l], h0.dtype).view(h0.shape))
-        return (dx, None, None, None, None, *out, *dh0s)
+        return (dx, None, None, None, None, *out, *[_gru_dh0(dh0_32[l], per[l][8]) for l in range(nl)])
 
 
 # ------------------------------------------------------------------ attention / head / loss

@@ -59,7 +59,7 @@ class ConvGRU(nn.Module):
     def run(self, x, T, shared_x, hidden=None):
         """x: [T*B,S,S,C] t-major (or [B,S,S,C] if shared_x).  Returns the list of per-layer
         sequences [T*B,S,S,h_l] (the reference returns the last step's list per call)."""
-        if Fn.ConvGRUStack.usable(x, self.cells):      # layer wavefront: all layers in one pass of grouped launches
+        if Fn.ConvGRUStack.usable(x, self.cells, T, shared_x, hidden):      # layer wavefront: all layers in one pass of grouped launches
             flat = []
             for c in self.cells:
                 flat += [c.update_gate.weight, c.update_gate.bias, c.reset_gate.weight, c.reset_gate.bias, c.out_gate.weight,

@@ -265,8 +265,11 @@ int dvd_conv_pick_nsplit(int dtype, long long M, int Cout, int C, int ntaps);
  * grouped launch one tile's epilogue runs under another's main loop and the 4 x 4 / 8 x 8 stages issue 2 instead of 6-12
  * dependent launches per step.  Results equal dvd_convgru_layer_* applied layer by layer (bit-equal when the split-K
  * factors are the same: `layer_policy`).  bf16, square power-of-two frames of 4, 8 or >= 16 pixels, 3 x 3 / 5 x 5 filters,
- * fragment-major weight images required: dvd_convgru_stack_ok() says whether a stack is served; callers fall back to the
- * per-layer entry points otherwise.
+ * fragment-major weight images required, and no grouped launch of the stack's schedule may need more than six members (four
+ * layers in steady state: 4 gate + 3 x-part convolutions in one launch on 4, 16 and 32 pixel frames -- not served; on 8 x 8 frames,
+ * or for sequences too short to fill the pipeline, they are).  dvd_convgru_stack_ok() says whether a stack is served -- it
+ * records the schedule the launch would play and needs no workspace; dvd_convgru_stack_ws_floats() answers 0 and both passes
+ * return DVD_E_SHAPE before any launch for a stack it refuses.  Callers fall back to the per-layer entry points otherwise.
  * ---------------------------------------------------------------------------------------- */
 #define DVD_GRU_STACK_MAX 4
 typedef struct {

@@ -265,6 +265,33 @@ def test_group_refusals_are_pinned(tmp_path):
     assert got == GROUP_REFUSALS
 
 
+def test_stack_schedule_is_pinned(tmp_path):
+    """The wavefront schedule of a ConvGRU stack (gru.hip: record_forward / record_backward) as the library records it before it
+    launches anything: every launch in issue order -- the elementwise gate kernels (kernel, hidden, step) and the grouped launches
+    (pass, kind, per member C, ldi, Cout, filter size, epilogue mode after the mode-6 rewrite, bias / res set, split-K factor and
+    slab offset in floats) -- plus the slab floats and the largest group of the pass.  tests/native/stack_schedule.cpp lists the
+    stacks: the generator's four ConvGRUs at B = 64, supplied initial states, B = 16, the per-layer policy with a split-K cap,
+    T = 1 and 2, one layer, and a four-layer stack with six-member groups (the coordinate-descent split-K search).  The program is
+    linked against the object files build.sh left, as in test_group_refusals_are_pinned; no GPU is touched.  The expected text was
+    printed by the commit before the schedule became a recorded value (profiles/gru_schedule_refactor_numbers.md says how)."""
+    import glob
+    import shutil
+    import subprocess
+    csrc = os.path.join(ROOT, "dvd_gan_amd", "csrc")
+    objs = sorted(glob.glob(os.path.join(csrc, "build", "*.o")))
+    if not objs or not shutil.which("hipcc"):
+        pytest.skip("no build/*.o or no hipcc: the library was not built by csrc/build.sh in this tree")
+    main_o, prog = str(tmp_path / "main.o"), str(tmp_path / "stack_schedule")
+    subprocess.check_call(["hipcc", "-x", "hip", "--cuda-host-only", "-std=c++17", "-I", csrc, "-c",
+                           os.path.join(ROOT, "tests", "native", "stack_schedule.cpp"), "-o", main_o])
+    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-o", prog, main_o] + objs)
+    got = subprocess.check_output([prog]).decode().splitlines()
+    want = open(os.path.join(ROOT, "tests", "native", "stack_schedule.txt")).read().splitlines()
+    assert len(want) > 500 and sum(l.startswith("==") for l in want) == 26
+    bad = [(i + 1, a, b) for i, (a, b) in enumerate(zip(got, want)) if a != b]
+    assert not bad and len(got) == len(want), (len(got), len(want), bad[:3])
+
+
 def test_attention_refusal_rules_need_no_gpu():
     """The shapes the attention entry points refuse before any launch (DVD_E_SHAPE): the MFMA kernels past 4096 tokens, the
     separable cell past an attended size of 64, the fp32 kernels' LDS limits -- forward [QB][Nk] scores + queries + partial
@@ -336,13 +363,13 @@ def test_convgru_stack_queries_need_no_gpu():
     from dvd_gan_amd import lib as L
     lib = L.lib()
 
-    def stack(S, hids, ks, dtype=L.BF16, B=64, T=48, cin0=256):
+    def stack(S, hids, ks, dtype=L.BF16, B=64, T=48, cin0=256, layer_policy=0, ns_cap=0):
         sd = L.GruStackDesc()
-        sd.n_layers = len(hids)
+        sd.n_layers, sd.layer_policy = len(hids), layer_policy
         for l, (h, k) in enumerate(zip(hids, ks)):
             d = sd.layer[l]
             d.dtype, d.T, d.B, d.H, d.W, d.hidden, d.k = dtype, T, B, S, S, h, k
-            d.gx_stride = B * S * S * 3 * h
+            d.gx_stride, d.ns_cap = B * S * S * 3 * h, ns_cap
             for f in ("gx", "w_ur", "w_o", "w_ur_q", "w_o_q", "wd_ur", "wd_o", "wd_ur_q", "wd_o_q", "h_all", "u_all", "r_all", "o_all",
                       "hr_all", "tickets", "dg", "carry"):
                 setattr(d, f, 1)                     # never dereferenced by the queries
@@ -376,6 +403,28 @@ def test_convgru_stack_queries_need_no_gpu():
         b = lib.dvd_convgru_stack_ws_floats(C.byref(sd))
         assert b >= 1 and b % 16384 == 0
     assert lib.dvd_convgru_stack_forward(C.byref(stack(12, [256], [3])), None) == -2
+    # a stack is served only if no grouped launch of its recorded schedule needs more than six members (kGroupMax, the limit of
+    # dvd_conv_forward_group: test_group_refusals_are_pinned).  Four layers in steady state on 16-pixel frames: 4 gate + 3 x-part
+    # members in the O group -> refused by every query instead of from the middle of the launch's time loop; at T = 2 the pipeline
+    # never fills; on 8 x 8 frames one x-part rides in the other group of a pair (5 and 6 members)
+    wsf = lambda sd: lib.dvd_convgru_stack_ws_floats(C.byref(sd))
+    four = stack(16, [64, 64, 64, 64], [3, 3, 3, 3])
+    assert ok(four) == 0 and ok(four, 1) == 0 and wsf(four) == 0
+    assert lib.dvd_convgru_stack_forward(C.byref(four), None) == -2 and lib.dvd_convgru_stack_backward(C.byref(four), None) == -2
+    short = stack(16, [64, 64, 64, 64], [3, 3, 3, 3], T=2)
+    assert ok(short) == 1 and ok(short, 1) == 1 and wsf(short) >= 1
+    four8 = stack(8, [256, 512, 256, 256], [3, 5, 3, 3])
+    assert ok(four8) == 1 and ok(four8, 1) == 1
+    # slab space of the benchmark's schedules (B = 64, T = 48, no h0, production policy unless stated): the answers of the library
+    # before the schedule became a recorded value
+    g, k = [256, 512, 256], [3, 5, 3]
+    assert wsf(stack(4, g, k)) == 7340032
+    assert wsf(stack(8, g, k)) == 14680064
+    assert wsf(stack(16, g, k)) == 12582912
+    assert wsf(stack(32, [128, 256, 128], [3, 5, 5])) == 16777216
+    assert wsf(four8) == 14680064
+    assert wsf(stack(4, g, k, layer_policy=1)) == 16777216
+    assert wsf(stack(4, g, k, ns_cap=2)) == 5767168
 
 
 def test_hot_kernels_use_no_scratch_memory():

@@ -23,6 +23,8 @@ CASES = [   # T, B, S, cin, hidden sizes, kernel sizes, shared input (first Conv
     (3, 2, 32, 8, [8, 16, 8], [3, 5, 5], False, None, 1),
     (3, 1, 32, 8, [16, 8], [5, 3], False, None, 1),            # two layers
     (2, 2, 16, 8, [16], [5], False, None, 1),                  # one layer: nothing to overlap, same entry point
+    # four layers: T = 8 is the shortest sequence at which all four layers and three x-parts share a launch (groups of 5 and 6)
+    (8, 2, 8, 16, [16, 32, 16, 16], [3, 5, 3, 3], False, (True, False, False, True), 1),
 ]
 
 
@@ -72,7 +74,7 @@ def test_wavefront_equals_layer_by_layer_bitwise(case, monkeypatch):
     monkeypatch.setattr(Fn, "GRU_STACK_LAYER_POLICY", 1)
     monkeypatch.setattr(Fn, "GRU_NS_CAP", case[8])               # ... and the same factors (at most the channel chunks of these narrow layers)
     monkeypatch.setattr(Fn, "GRU_STACK", True)
-    assert Fn.ConvGRUStack.usable(torch.empty(1, case[2], case[2], 8, dtype=torch.bfloat16), gru.cells)
+    assert Fn.ConvGRUStack.usable(torch.empty(1, case[2], case[2], 8, dtype=torch.bfloat16), gru.cells, case[0], case[6])
     new = _run(gru, case, x, gys, h0s, all_layers=False)
     assert int(L.gru_tickets(torch.device(DEV, torch.cuda.current_device())).abs().sum()) == 0
     again = _run(gru, case, x, gys, h0s, all_layers=False)
@@ -93,6 +95,7 @@ WIDE = [    # layers wide enough for the production split-K policy to split memb
     (3, 1, 32, 32, [64, 128, 64], [3, 5, 5], False, (True, False, True), 0),
     (3, 4, 8, 64, [128, 256, 128], [3, 5, 3], False, None, 0),
     (3, 8, 4, 64, [128, 256, 128], [3, 5, 3], True, None, 0),
+    (8, 4, 8, 64, [128, 256, 128, 128], [3, 5, 3, 3], False, None, 0),      # six-member groups: the coordinate-descent split-K plans
 ]
 
 
@@ -113,6 +116,36 @@ def test_wavefront_production_policy_and_outer_gradients(case, monkeypatch):
         assert _rel(a, b) < 1e-2
     for (k, _), a, b in zip(gru.named_parameters(), new["dw"], old["dw"]):
         assert _rel(a, b) < 1e-2, (k, _rel(a, b))
+
+
+def test_four_layers_are_refused_up_front_or_served(monkeypatch):
+    """Four layers on 16 x 16 frames.  At T = 8 the O group of the steady state would hold 4 gate + 3 x-part convolutions, one more
+    than a grouped launch takes: the library says so BEFORE anything is launched (`usable` is its answer), ConvGRU.run takes the
+    layer-by-layer path and returns what GRU_STACK = False returns, bit for bit.  At T = 2 the pipeline never fills, the wavefront
+    serves the stack, and with the layer path's split-K factors it is bit-equal to it (weight gradients up to the fp32 atomics
+    of these narrow layers, as in test_wavefront_equals_layer_by_layer_bitwise)."""
+    from dvd_gan_amd import functional as Fn
+    for T, served in ((8, False), (2, True)):
+        case = (T, 2, 16, 8, [8, 16, 8, 8], [3, 5, 3, 3], False, None, 1)
+        gru, x, gys, h0s = _build(case)
+        monkeypatch.setattr(Fn, "GRU_COMBINE_MAX", 8 if served else 0)
+        monkeypatch.setattr(Fn, "GRU_STACK_LAYER_POLICY", 1 if served else 0)
+        monkeypatch.setattr(Fn, "GRU_NS_CAP", 1 if served else 0)
+        monkeypatch.setattr(Fn, "GRU_STACK", True)
+        xc = torch.empty(T * 2, 16, 16, 8, dtype=torch.bfloat16)
+        assert Fn.ConvGRUStack.usable(xc, gru.cells, T, False) is served
+        new = _run(gru, case, x, gys, h0s, all_layers=False)
+        monkeypatch.setattr(Fn, "GRU_STACK", False)
+        old = _run(gru, case, x, gys, h0s, all_layers=False)
+        for l, (a, b) in enumerate(zip(new["ys"], old["ys"])):
+            assert torch.equal(a, b), f"T={T} layer {l}: states differ (rel {_rel(a, b):.3e})"
+        assert torch.equal(new["dx"], old["dx"]), f"T={T}: dx differs (rel {_rel(new['dx'], old['dx']):.3e})"
+        for (k, _), a, b in zip(gru.named_parameters(), new["dw"], old["dw"]):
+            print(f"T={T} {k}: rel {_rel(a, b):.3e}")
+            if served:
+                assert _rel(a, b) < 1e-5, (k, _rel(a, b))
+            else:
+                assert torch.equal(a, b), (T, k, _rel(a, b))
 
 
 def test_wavefront_inference_form(monkeypatch):
