@@ -10,6 +10,19 @@ Split of work:
       [T, S, S, 3] -> [3, T, S, S] layout change, one pass, into the fp32 [B, 3, T, S, S] batch `Trainer.train_step` takes.
 Random draws come from Python's `random` in the reference's order (temporal crop, then scale, crop position, flip), so a seeded
 run reproduces the reference's clips bit for bit (tests/test_gpu_data.py, fixture F12).
+
+Second path, for data that fits in device memory (`ClipStore`, `make_store_loader`; tests/test_gpu_clipstore.py): the host reader
+above decodes and resizes every frame of every step on DataLoader workers (measured on small synthetic JPEGs: 16 workers deliver
+about six times the benchmark step's clip rate; the store, with no worker at all, fifty times that: profiles/clipstore_numbers.md).
+Split of work there:
+  host, once (`ClipStore.build`): every frame of every video decoded with the reader's own PIL call and packed into one uint8 blob
+      [frame][h][w][3] that lives on the device, plus per-video (offset, h, w, frames) and per-record (video, label, window);
+  host, per step (`make_store_loader`): the reader's random draws in the reader's order -- temporal crop, scale, position, flip --
+      turned into an integer crop box per clip with the reader's own expressions and PIL's rounding, the coefficient tables of
+      PIL's 8-bit bilinear resize for every new (crop side, output side) pair (`resize_coeffs`, fp64, cached on the device), and ONE
+      small upload of the clip rows and frame indices;
+  device, per step (`ClipStore.gather`, kernel dvd_clip_gather): crop, the two integer resize passes, flip, normalise and layout
+      in one launch.  The bytes equal the host reader's: PIL's 8-bit resize is integer arithmetic on those tables.
 """
 import ctypes as C
 import json
@@ -84,27 +97,29 @@ class MultiScaleCrop:
         else:
             self.crop_position = self.positions[random.randint(0, len(self.positions) - 1)]
 
-    def __call__(self, img):
-        from PIL import Image
-        w, h = img.size
+    def box(self, w, h):
+        """The crop box (left, upper, right, lower) for a w x h frame under the drawn parameters, as handed to `img.crop`
+        (floats in 'random' mode: crop rounds them half to even)."""
         crop = int(min(w, h) * self.scale)
         if self.mode == "random":
             x1, y1 = self.tl_x * (w - crop), self.tl_y * (h - crop)
-            box = (x1, y1, x1 + crop, y1 + crop)
-        else:
-            p = self.crop_position
-            if p == "c":
-                cx, cy, half = w // 2, h // 2, crop // 2
-                box = (cx - half, cy - half, cx + half, cy + half)
-            elif p == "tl":
-                box = (0, 0, crop, crop)
-            elif p == "tr":
-                box = (w - crop, 0, w, crop)
-            elif p == "bl":
-                box = (0, h - crop, crop, h)
-            else:
-                box = (w - crop, h - crop, w, h)
-        return img.crop(box).resize((self.size, self.size), Image.BILINEAR)
+            return (x1, y1, x1 + crop, y1 + crop)
+        p = self.crop_position
+        if p == "c":
+            cx, cy, half = w // 2, h // 2, crop // 2
+            return (cx - half, cy - half, cx + half, cy + half)
+        if p == "tl":
+            return (0, 0, crop, crop)
+        if p == "tr":
+            return (w - crop, 0, w, crop)
+        if p == "bl":
+            return (0, h - crop, crop, h)
+        return (w - crop, h - crop, w, h)
+
+    def __call__(self, img):
+        from PIL import Image
+        w, h = img.size
+        return img.crop(self.box(w, h)).resize((self.size, self.size), Image.BILINEAR)
 
 
 def default_scales(initial_scale=1.0, n_scales=5, scale_step=0.84089641525):     # main.py:38-40, parameter.py:73-75
@@ -189,3 +204,253 @@ def make_loader(dataset, batch_size, num_workers=0, shuffle=True, device=None, r
             for clips, flips, labels in loader:
                 yield clips_to_device(clips, flips, dev), labels
     return _OnDevice()
+
+
+# ------------------------------------------------------------------ device-resident clip store
+PRECISION_BITS = 22         # Resample.c: 8-bit coefficients are scaled by 2^22, accumulators start at 2^21
+
+
+def resize_coeffs(in_size, out_size):
+    """Pillow's coefficient table for resampling in_size -> out_size samples of an 8-bit image with the bilinear filter
+    (Resample.c: precompute_coeffs + normalize_coeffs_8bpc, fp64 like there).  -> (bounds int32 [out, 2] = first source sample and
+    count per output sample, coefficients int32 [out, ksize], zero past the count).  Bilinear weights are never negative."""
+    import numpy as np
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = fs                                            # filter support 1.0 * filterscale
+    ksize = 2 * int(math.ceil(support)) + 1
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    kk = np.zeros((out_size, ksize), dtype=np.int32)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(0, int(center - support + 0.5))
+        xmax = min(in_size, int(center + support + 0.5)) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) / fs)) for x in range(xmax)]
+        ww = 0.0
+        for v in w:                                         # summed in order, like the C loop
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        bounds[xx] = xmin, xmax
+        kk[xx, :xmax] = [int(0.5 + v * (1 << PRECISION_BITS)) for v in w]
+    return bounds, kk
+
+
+def crop_box(crop, w, h):
+    """The integer box (x0, y0, cw, ch) `crop(img)` cuts from a w x h frame: MultiScaleCrop.box rounded as Image.crop rounds it
+    (Python's round: half to even), so in 'random' mode cw and ch are each crop - 1, crop or crop + 1, independently."""
+    x0, y0, x1, y1 = (int(round(v)) for v in crop.box(w, h))
+    return x0, y0, x1 - x0, y1 - y0
+
+
+class ClipStore:
+    """Every frame of a `UCF101` dataset decoded once into one uint8 blob [frame][h][w][3] ON THE DEVICE, with the tables that find
+    a record's frames in it; `gather` cuts a batch of clips from it in one kernel launch (dvd_clip_gather).  The whole blob must fit
+    in the memory of one device next to the model (UCF-101 at 240 x 320 is 2.5 M frames = 580 GB: use `prescale`; at a short side
+    of 64 it is 41 GB); stores larger than device memory, or kept in host memory, are not served -- `make_loader` is the path for
+    those.
+
+    Tensors (what `save` writes): blob uint8 [bytes]; video_offset int64, video_h / video_w / video_frames int32 [videos];
+    record_video / record_label / record_first / record_last int64 [records] (first / last: the 1-based frame numbers that bound
+    the record's `frame_indices`; the windows of n_samples_for_each_video > 1 point into the same stored video)."""
+
+    FIELDS = ("blob", "video_offset", "video_h", "video_w", "video_frames", "record_video", "record_label", "record_first",
+              "record_last")
+
+    def __init__(self, **tensors):
+        assert set(tensors) == set(self.FIELDS), sorted(set(tensors) ^ set(self.FIELDS))
+        for k, v in tensors.items():
+            setattr(self, k, v)
+        self._videos = list(zip(self.video_offset.tolist(), self.video_h.tolist(), self.video_w.tolist(), self.video_frames.tolist()))
+        self._records = list(zip(self.record_video.tolist(), self.record_label.tolist(), self.record_first.tolist(),
+                                 self.record_last.tolist()))
+        self._tables, self._pool, self._pool_used, self._ms = {}, None, 0, {}
+
+    def __len__(self):
+        return len(self._records)
+
+    @property
+    def device(self):
+        return self.blob.device
+
+    def record(self, index):
+        """-> (label, first frame number, last frame number, h, w) of record `index`."""
+        video, label, first, last = self._records[index]
+        return label, first, last, self._videos[video][1], self._videos[video][2]
+
+    @classmethod
+    def build(cls, dataset, prescale=None, device="cpu"):
+        """Decode every frame `image_00001 .. image_{n_frames}` of every distinct video of `dataset` (a `UCF101`) with the reader's
+        call, `Image.open(f).convert("RGB")`.  A video with a missing frame file, or with frames of different sizes, raises (the
+        host reader silently returns a short clip there, which cannot be batched).
+        prescale=P: every frame is resized with PIL bilinear so that its short side is P (the long side int(P * long / short))
+        before it is stored.  This CHANGES THE PIXELS relative to the host reader, which crops the original frames: only a store
+        built with prescale=None reproduces the reader bit for bit."""
+        import numpy as np
+        from PIL import Image
+        videos, frames, tables, records = {}, [], [], []
+        offset = 0
+        for rec in dataset.data:
+            folder = rec["video"]
+            if folder not in videos:
+                size, n = None, int(rec["n_frames"])
+                for i in range(1, n + 1):
+                    path = os.path.join(folder, "image_{:05d}.jpg".format(i))
+                    if not os.path.exists(path):
+                        raise FileNotFoundError(f"{path}: frame {i} of {n} is missing (ClipStore needs every frame of a video)")
+                    with open(path, "rb") as f, Image.open(f) as img:
+                        img = img.convert("RGB")
+                        if prescale is not None:
+                            w, h = img.size
+                            to = (prescale, int(prescale * h / w)) if w <= h else (int(prescale * w / h), prescale)
+                            img = img.resize(to, Image.BILINEAR)
+                        a = np.asarray(img, dtype=np.uint8)
+                    if size is None:
+                        size = a.shape
+                    elif a.shape != size:
+                        raise ValueError(f"{path}: frame size {a.shape[:2]} differs from the video's {size[:2]}")
+                    frames.append(a.reshape(-1))
+                videos[folder] = len(tables)
+                tables.append((offset, size[0], size[1], n))
+                offset += n * size[0] * size[1] * 3
+            ids = rec["frame_indices"]
+            records.append((videos[folder], rec["label"], ids[0], ids[-1]))
+        blob = torch.from_numpy(np.concatenate(frames)) if frames else torch.empty(0, dtype=torch.uint8)
+        col = lambda rows, j, dtype: torch.tensor([r[j] for r in rows], dtype=dtype)
+        return cls(blob=blob.to(device), video_offset=col(tables, 0, torch.int64), video_h=col(tables, 1, torch.int32),
+                   video_w=col(tables, 2, torch.int32), video_frames=col(tables, 3, torch.int32),
+                   record_video=col(records, 0, torch.int64), record_label=col(records, 1, torch.int64),
+                   record_first=col(records, 2, torch.int64), record_last=col(records, 3, torch.int64))
+
+    def save(self, path):
+        """One file of plain tensors (torch.save of a dict; `load` reads it with weights_only=True)."""
+        torch.save({k: getattr(self, k).cpu() for k in self.FIELDS}, path)
+
+    @classmethod
+    def load(cls, path, device):
+        """The store `save` wrote, its blob on `device` (the tables stay on the host: only the draws read them)."""
+        t = torch.load(path, map_location="cpu", weights_only=True)
+        t["blob"] = t["blob"].to(device)
+        return cls(**t)
+
+    def to(self, device):
+        return ClipStore(**{k: getattr(self, k).to(device) if k == "blob" else getattr(self, k) for k in self.FIELDS})
+
+    def _table(self, in_size, out_size):
+        """Position (in ints) of the coefficient table in_size -> out_size in the device pool; built and uploaded on first use (a
+        training run needs a handful: five scales, in 'random' mode three widths each)."""
+        from .helpers import to_device_async
+        pos = self._tables.get((in_size, out_size))
+        if pos is None:
+            bounds, kk = resize_coeffs(in_size, out_size)
+            flat = torch.cat([torch.from_numpy(bounds).reshape(-1), torch.from_numpy(kk).reshape(-1)])
+            need = self._pool_used + flat.numel()
+            if self._pool is None or need > self._pool.numel():
+                pool = torch.zeros(max(1 << 16, 2 * need), dtype=torch.int32, device=self.device)
+                if self._pool is not None:
+                    pool[:self._pool_used].copy_(self._pool[:self._pool_used])
+                self._pool = pool
+            self._pool[self._pool_used:need].copy_(to_device_async(flat, self.device))
+            pos = self._tables[(in_size, out_size)] = self._pool_used
+            self._pool_used = need
+        return pos
+
+    def gather(self, record_ids, frame_ids, boxes, flips, size, norm_value=255.0, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)):
+        """The batch of clips -> fp32 [B, 3, T, size, size] on the store's device, one launch, nothing waited for: per clip b the
+        record index record_ids[b], its T frame numbers frame_ids[b] (1-based, as in the file names and `frame_indices`), the
+        integer crop box boxes[b] = (x0, y0, cw, ch) inside the frame and the flip flag flips[b]; each frame is cropped, resized
+        with PIL's 8-bit bilinear arithmetic, mirrored if flagged and written as ((v / norm_value) - mean) / std: the bytes of
+        `clips_to_device` on the host reader's clip."""
+        from . import kern as K
+        from .helpers import to_device_async
+        B, T = len(record_ids), len(frame_ids[0])
+        if not self.blob.is_cuda:
+            raise RuntimeError("ClipStore.gather needs the blob on the GPU (ClipStore.load(path, device) / .to(device)): there is "
+                               "no CPU path")
+        head, tail = [], []                              # B rows of L.CLIP_COLS columns, then the B * T frame indices
+        for b in range(B):
+            off, h, w, n = self._videos[self._records[record_ids[b]][0]]
+            x0, y0, cw, ch = (int(v) for v in boxes[b])
+            if not (0 < cw and 0 < ch and 0 <= x0 <= w - cw and 0 <= y0 <= h - ch):
+                raise ValueError(f"clip {b}: box {tuple(boxes[b])} is not inside the {w} x {h} frame")
+            if len(frame_ids[b]) != T:
+                raise ValueError(f"clip {b}: {len(frame_ids[b])} frames, the batch has {T} (short clips cannot be batched)")
+            head += [off, h, w, n, x0, y0, cw, ch, int(bool(flips[b])), self._table(cw, size), self._table(ch, size)]
+            tail += [int(f) - 1 for f in frame_ids[b]]
+        rows = torch.tensor(head + tail, dtype=torch.int64)
+        key = (float(norm_value), tuple(mean), tuple(std))
+        if key not in self._ms:
+            self._ms[key] = to_device_async(torch.tensor(list(mean) + list(std), dtype=torch.float32), self.device)
+        out = torch.empty(B, 3, T, size, size, dtype=torch.float32, device=self.device)
+        return K.clip_gather(self.blob, rows, to_device_async(rows, self.device), self._pool, out, self._ms[key], norm_value)
+
+
+class StoreLoader:
+    """What `make_store_loader` returns: len / iter / set_epoch like `make_loader`'s object, plus `plan_epoch` and `batch`."""
+
+    def __init__(self, store, batch_size, n_frames, crop, shuffle, sampler):
+        self.store, self.batch_size, self.n_frames, self.crop, self.shuffle, self.sampler = store, batch_size, n_frames, crop, shuffle, sampler
+
+    def __len__(self):
+        n = len(self.sampler) if self.sampler is not None else len(self.store)
+        return n // self.batch_size
+
+    def set_epoch(self, epoch):
+        if self.sampler is not None:
+            self.sampler.set_epoch(epoch)
+
+    def plan_epoch(self):
+        """The record indices of every batch of one epoch, in order; touches no device.  (Single process with shuffle: draws a
+        permutation from torch's default generator, so every call gives another one.)"""
+        if self.sampler is not None:
+            order = list(self.sampler)
+        elif self.shuffle:
+            order = torch.randperm(len(self.store)).tolist()
+        else:
+            order = list(range(len(self.store)))
+        B = self.batch_size
+        return [order[i:i + B] for i in range(0, len(order) - B + 1, B)]
+
+    def draw(self, record_ids):
+        """The reader's draws from Python's `random` for these records, one record after the other, each in the order of
+        UCF101.__getitem__: temporal crop (cyclic repeat of short windows included), scale, position (or the two random() of
+        'random' mode), flip.  -> (frame numbers [B][T], boxes [B] = (x0, y0, cw, ch), flips [B], labels [B])."""
+        frames, boxes, flips, labels = [], [], [], []
+        for index in record_ids:
+            label, first, last, h, w = self.store.record(index)
+            frames.append(temporal_random_crop(list(range(first, last + 1)), self.n_frames))
+            self.crop.randomize_parameters()
+            flips.append(random.random() < 0.5)
+            boxes.append(crop_box(self.crop, w, h))
+            labels.append(label)
+        return frames, boxes, flips, labels
+
+    def batch(self, record_ids):
+        """-> (fp32 [B, 3, T, S, S] on the store's device, labels [B]) for these records, drawn as `draw` says."""
+        frames, boxes, flips, labels = self.draw(record_ids)
+        return self.store.gather(record_ids, frames, boxes, flips, self.crop.size), torch.tensor(labels)
+
+    def __iter__(self):
+        for record_ids in self.plan_epoch():
+            yield self.batch(record_ids)
+
+
+def make_store_loader(store, batch_size, n_frames, sample_size, scales=None, train_crop="corner", shuffle=True, rank=None,
+                      world=None, seed=0):
+    """`make_loader` for a `ClipStore`: batches are (fp32 [B, 3, T, S, S] on the store's device, labels [B]) -- what Trainer.train
+    expects --, the last, incomplete batch is dropped, and the clips are the ones `UCF101(n_frames, sample_size, scales, train_crop)`
+    yields for the same records under the same state of Python's `random`, bit for bit: the draws are made per sample, in the
+    batch's record order, exactly as UCF101.__getitem__ makes them (so with shuffle=False and num_workers=0 the two loaders agree
+    batch by batch).  The host only draws and uploads one small block per batch; it never waits for the device.
+    Sample order: shuffle=False: record order.  Data parallel (rank / world given, or read from torch.distributed): the same
+    DistributedSampler(seed, drop_last=True) as `make_loader`, so the rank splits are identical; call `set_epoch(e)` per epoch.
+    Single process with shuffle=True: a permutation from torch's default generator -- NOT promised to be the order DataLoader's
+    RandomSampler would give from the same generator state."""
+    if world is None and torch.distributed.is_available() and torch.distributed.is_initialized():
+        world, rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
+    sampler = None
+    if world is not None and world > 1:
+        sampler = data.distributed.DistributedSampler(range(len(store)), num_replicas=world, rank=rank, shuffle=shuffle, seed=seed,
+                                                      drop_last=True)
+    return StoreLoader(store, batch_size, n_frames, MultiScaleCrop(scales or default_scales(), sample_size, train_crop), shuffle,
+                       sampler)

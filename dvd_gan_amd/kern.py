@@ -637,3 +637,18 @@ def frame_metrics(pred, p_strides, target, t_strides, B, T, Cc, H, W, flags, mse
     L.check(lib.dvd_frame_metrics(C.c_void_p(pred.data_ptr()), *(_ll(s) for s in p_strides),
                                   C.c_void_p(target.data_ptr()), *(_ll(s) for s in t_strides),
                                   _ll(B), T, Cc, H, W, int(flags), L.ptr(mse), L.ptr(ssim), L.ptr(ws), L.stream()))
+
+
+def clip_gather(blob, clips_host, clips_dev, tables, out, ms, norm_value=255.0):
+    """dvd_clip_gather: uint8 device blob of decoded frames -> `out` fp32 [B, 3, T, S, S] (crop, Pillow's 8-bit bilinear resize,
+    flip, normalise, layout in one launch).  clips_host / clips_dev: the same int64 values on the host (checked there before any
+    launch) and on the device -- B rows of lib.CLIP_COLS columns, then the B * T frame indices; tables: the device int32 pool the
+    rows' CLIP_XTAB / CLIP_YTAB point into; ms: device float[6] = mean RGB | std RGB."""
+    B, three, T, S, S2 = out.shape
+    assert three == 3 and S == S2 and out.dtype == torch.float32 and blob.dtype == torch.uint8 and tables.dtype == torch.int32
+    assert clips_host.dtype == clips_dev.dtype == torch.int64 and not clips_host.is_cuda and clips_host.is_contiguous()
+    assert clips_host.numel() == clips_dev.numel() == B * (L.CLIP_COLS + T)
+    L.check(L.lib().dvd_clip_gather(L.ptr(blob), _ll(blob.numel()), C.c_void_p(clips_host.data_ptr()), L.ptr(clips_dev),
+                                    L.ptr(tables), _ll(tables.numel()), L.ptr(out), _ll(B), T, S, _f(norm_value), L.ptr(ms),
+                                    L.stream()))
+    return out

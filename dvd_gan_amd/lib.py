@@ -68,6 +68,10 @@ def lib():
 ABI_VERSION = 13
 BN_NREP = 16            # DVD_BN_NREP of include/dvdgan_hip.h
 SN_SCRATCH = 512        # DVD_SN_SCRATCH
+# dvd_clip_gather: columns of a clip row (DVD_CLIP_*), served sizes
+CLIP_COLS = 11
+(CLIP_OFF, CLIP_H, CLIP_W, CLIP_FRAMES, CLIP_X0, CLIP_Y0, CLIP_CW, CLIP_CH, CLIP_FLIP, CLIP_XTAB, CLIP_YTAB) = range(CLIP_COLS)
+CLIP_MAX_SIDE, CLIP_MAX_OUT = 4096, 256
 
 
 def check(code):

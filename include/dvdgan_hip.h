@@ -568,6 +568,44 @@ int dvd_sepattn_backward(int dtype, const void* dy, int ldx, int C, int Cq, cons
 int dvd_clip_to_tensor(const unsigned char* src, const unsigned char* flip, float* dst, long long B, int T, int H, int W,
                        float norm_value, const float* mean_std, void* stream);
 
+/* Device-resident clip store (data.ClipStore.gather; the whole per-step work of Dataloader/datasets/ucf101.py:37-46,178-199 with
+ * the training transforms of main.py:42-55 after the JPEG decode; additions: the ABI version stays 13).  `blob`: decoded uint8
+ * frames, per video [frame][h][w][3], any byte alignment.  One launch writes fp32 dst [B][3][T][S][S]: for clip b the frames
+ * `frame[b][t]` of its video, cropped to the integer box (x0, y0, cw, ch) -- cw != ch allowed --, resized to S x S exactly like
+ * Pillow's 8-bit `resize(..., BILINEAR)` (integer arithmetic: acc = 2^21 + sum pix * k, clamp(acc >> 22, 0, 255); the horizontal
+ * pass first, rounded to uint8, then the vertical pass on those bytes), mirrored in x when flip != 0, then
+ * ((v / norm_value) - mean[c]) / std[c] as dvd_clip_to_tensor writes it.
+ * `clips`: long long [B][DVD_CLIP_COLS] followed by the frame indices long long [B][T] (0-based within the video), given twice:
+ * in host memory (every check below reads it, before any launch) and the same values in device memory.
+ * `tables`: device int32 pool of coefficient tables; the table for in -> S samples at position p is [S][2] (first source sample,
+ * count) then [S][ksize] coefficients scaled by 2^22, ksize = 2 * ceil(max(in / S, 1)) + 1, made by Pillow's rule in fp64
+ * (data.resize_coeffs).  DVD_CLIP_XTAB / _YTAB = positions (in ints) of the tables for cw -> S and ch -> S.  The contents are the
+ * caller's responsibility; whatever they hold, no read leaves the crop box.
+ * Served: frame sides <= DVD_CLIP_MAX_SIDE, S <= DVD_CLIP_MAX_OUT, B * T < 2^31; a workgroup handles a band of output rows of one
+ * frame whose horizontally resized source rows fit 64 KB of LDS (dvd_clip_gather_band_rows(ch, S) = rows per band, the smallest
+ * over the batch is used; 0 = not served: never within the limits above).  DVD_E_SHAPE outside that.
+ * DVD_E_ARG: a null pointer, a non-positive size or norm_value == 0, a box outside its frame, a video outside the blob
+ * (offset + frames * h * w * 3 > blob_bytes), a frame index outside its video, a table position outside the pool.
+ * Deterministic: no atomics, a frame's result depends on that frame, its box and its tables alone. */
+#define DVD_CLIP_COLS 11
+#define DVD_CLIP_OFF 0        /* byte offset of the video's first frame in the blob */
+#define DVD_CLIP_H 1
+#define DVD_CLIP_W 2
+#define DVD_CLIP_FRAMES 3     /* frames of the video */
+#define DVD_CLIP_X0 4
+#define DVD_CLIP_Y0 5
+#define DVD_CLIP_CW 6
+#define DVD_CLIP_CH 7
+#define DVD_CLIP_FLIP 8
+#define DVD_CLIP_XTAB 9
+#define DVD_CLIP_YTAB 10
+#define DVD_CLIP_MAX_SIDE 4096
+#define DVD_CLIP_MAX_OUT 256
+int dvd_clip_gather_band_rows(int crop_h, int S);
+int dvd_clip_gather(const unsigned char* blob, long long blob_bytes, const long long* clips_host, const long long* clips_dev,
+                    const int* tables, long long table_ints, float* dst, long long B, int T, int S, float norm_value,
+                    const float* mean_std, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
