@@ -286,6 +286,8 @@ def conv_wgrad(x, dy, dw, ksize, cout, cin_real, *, up2=False, relu_in=False, ms
     ntaps = k[0] * k[1] * k[2]
     esz = x.element_size()
     ci_tot = dw_ci_tot if dw_ci_tot is not None else cin_real
+    if dy_col % 8 or dw_ci_off + cin_real > ci_tot:      # dy is read in 16-byte vectors from the shifted pointer; the window lies inside dw
+        raise ValueError(f"conv_wgrad: dy_col {dy_col} is not a multiple of 8, or dw window [{dw_ci_off}, {dw_ci_off + cin_real}) exceeds {ci_tot}")
     d = L.WgradDesc()
     d.dtype, d.frames, d.T, d.H, d.W = L.dt(x), F_, T, H, W
     d.C, d.ldx, d.Cin_real = x.shape[-1], x.shape[-1], cin_real

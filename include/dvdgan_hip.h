@@ -202,7 +202,8 @@ int dvd_to_channels_last(int dtype, const float* src, void* dst, long long F, in
                          int Cp, int A, int B, int swap_ab, void* stream);
 int dvd_from_channels_last(int dtype, const void* src, float* dst, long long F, int C, long long P,
                            int Cp, int A, int B, int swap_ab, void* stream);
-/* dst[i] (+)= (float)src[i] * alpha, n elements; src/dst dtype given separately */
+/* dst[i] = (dst type)src[i], n elements (any n: eight per thread, then a scalar tail); src / dst dtype given separately
+ * (fp32 -> bf16 rounds to nearest even).  No scaling and no accumulation: dst is overwritten. */
 int dvd_convert(int src_dtype, const void* src, int dst_dtype, void* dst, long long n, void* stream);
 
 
