@@ -654,3 +654,27 @@ def clip_gather(blob, clips_host, clips_dev, tables, out, ms, norm_value=255.0):
                                     L.ptr(tables), _ll(tables.numel()), L.ptr(out), _ll(B), T, S, _f(norm_value), L.ptr(ms),
                                     L.stream()))
     return out
+
+
+SHEET_FILL, SHEET_SIGNED = 1, 2                  # DVD_SHEET_* of include/dvdgan_hip.h
+
+
+def sample_sheet_shape(total_slots, H, W, nrow, padding, row_prefix=0):
+    """dvd_sample_sheet_shape -> (Hs, Ws, bytes of one sheet) of make_grid's geometry; needs no GPU.  ValueError when refused."""
+    hs, ws, nb = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    rc = L.lib().dvd_sample_sheet_shape(int(total_slots), int(H), int(W), int(nrow), int(padding), int(row_prefix),
+                                        C.byref(hs), C.byref(ws), C.byref(nb))
+    if rc != 0:
+        raise ValueError(f"no sheet of {total_slots} slots of {H} x {W}, nrow={nrow}, padding={padding}: "
+                         f"{L.lib().dvd_strerror(rc).decode()} (code {rc})")
+    return hs.value, ws.value, nb.value
+
+
+def sample_sheet(src, strides, n_sheets, n_tiles, H, W, first_slot, total_slots, nrow, padding, pad_value, row_prefix, flags, dst):
+    """dvd_sample_sheet: device fp32 `src` (views welcome: only the data pointer is taken) seen as [n_sheets][n_tiles][3][H][W]
+    with (sheet, tile, channel) `strides` in elements -> the uint8 device buffer `dst` [n_sheets][Hs][row_prefix + 3 Ws]."""
+    assert src.is_cuda and src.dtype == torch.float32 and dst.dtype == torch.uint8 and dst.device == src.device
+    L.check(L.lib().dvd_sample_sheet(C.c_void_p(src.data_ptr()), *(_ll(s) for s in strides), _ll(n_sheets), int(n_tiles), int(H),
+                                     int(W), int(first_slot), int(total_slots), int(nrow), int(padding), _f(pad_value),
+                                     int(row_prefix), int(flags), L.ptr(dst), L.stream()))
+    return dst

@@ -22,7 +22,13 @@ config.g_clip_norm / d_clip_norm > 0 clip the gradient of G / of D_s and D_t (ea
 config.skip_nonfinite leaves a network's weights and Adam state untouched in a step whose gradient holds an inf or a NaN,
 config.grad_log = R keeps the last R steps' norms -- all on the device (optim.FlatAdam's guard): `grad_norms` are device scalars,
 `guard_report()` is the one call that reads them back.
-Out of scope: tensorboard logging, sample grids, dataset loaders.
+config.sample_step = N > 0 (or the reference's sample_epoch) writes sample sheets every N steps (trainer.py:186,195-197,323-334):
+`save_samples` runs eval-mode G on the fixed noise of `fixed_inputs()`, one HIP launch turns the clips into 8-bit sheets
+(sheets.make_sheets) and a sheets.SheetWriter compresses and writes them on a worker thread -- one PNG per clip under the
+reference's names, and / or one animated PNG of all clips (config.sample_layout).  `save_predictions` writes real-against-predicted
+comparison sheets of a frame-conditional generator, `save_real` the loader's clips.  None of them leaves a trace in the training
+state or in the default generator.
+Out of scope: tensorboard logging, GIF / MP4 files, dataset loaders.
 """
 import contextlib
 import os
@@ -154,6 +160,23 @@ class Trainer(object):
         self.model_save_path = os.path.join(getattr(c, "model_save_path", "./models"), getattr(c, "version", ""))
         self.model_save_epoch = getattr(c, "model_save_epoch", 0)
         self.log_epoch = getattr(c, "log_epoch", 1)
+        # sample sheets (sample_step = sample_epoch = 0: off): period in steps, or in epochs like the reference (trainer.py:186);
+        # directory (trainer.py:69); clips per class; "frames" = a PNG per clip, "clips" = one animation of all clips, "both"
+        self.sample_step = int(getattr(c, "sample_step", 0) or 0)
+        self.sample_epoch = getattr(c, "sample_epoch", 0) or 0
+        self.sample_path = os.path.join(getattr(c, "sample_path", "./samples"), getattr(c, "version", ""))
+        self.test_batch_size = int(getattr(c, "test_batch_size", 8))
+        self.sample_layout = getattr(c, "sample_layout", "frames")
+        self.sample_fps = getattr(c, "sample_fps", 8)
+        self.sample_use_ema = bool(getattr(c, "sample_use_ema", False))
+        self.sample_seed = int(getattr(c, "sample_seed", 0))
+        if (self.sample_step < 0 or self.sample_epoch < 0 or self.test_batch_size < 1 or not self.sample_fps > 0
+                or self.sample_layout not in ("frames", "clips", "both")):
+            raise ValueError(f"sample_step={self.sample_step}, sample_epoch={self.sample_epoch} (>= 0), "
+                             f"test_batch_size={self.test_batch_size} (>= 1), sample_fps={self.sample_fps} (> 0), "
+                             f"sample_layout={self.sample_layout!r} ('frames' | 'clips' | 'both')")
+        self._fixed = None            # fixed_inputs(), drawn at first use
+        self._sheets = None           # the sheets.SheetWriter, made at first use
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.compute_dtype, self.latent_dim = compute_dtype, latent_dim
         Fn.direct_weight_grads(True)          # weight gradients accumulate into FlatAdam's buffers on a side stream
@@ -436,7 +459,7 @@ class Trainer(object):
         self.g_lr_scher.step((g_s_loss + g_t_loss) if self._plateau else None)
         return ds_loss_real, ds_loss_fake, dt_loss_real, dt_loss_fake, g_s_loss, g_t_loss
 
-    # ---- trainer.py:189-343 (loop; logging reduced to a print, no sampling)
+    # ---- trainer.py:189-343 (loop; logging reduced to a print)
     def _new_epoch(self):
         """-> iterator over the loader for the next epoch.  A rank-sharded loader (data.make_loader: DistributedSampler) shuffles
         with seed + epoch: without set_epoch every epoch would repeat the same order and the same rank split."""
@@ -455,24 +478,204 @@ class Trainer(object):
         data_iter = self._new_epoch()
         self.D_s.train(); self.D_t.train(); self.G.train()
         t0 = time.time()
-        for step in range(start, total_step + 1):
+        # sample sheets: every sample_step steps, or every sample_epoch epochs (trainer.py:186); 0 = never, nothing is set up
+        sample_step = getattr(self, "sample_step", 0) or int(getattr(self, "sample_epoch", 0) * steps_per_epoch)
+        try:
+            for step in range(start, total_step + 1):
+                try:
+                    real_videos, real_labels = next(data_iter)
+                except StopIteration:
+                    data_iter = self._new_epoch()
+                    real_videos, real_labels = next(data_iter)
+                losses = self.train_step(real_videos, real_labels)
+                if self.log_epoch and step % (self.log_epoch * steps_per_epoch) == 0:
+                    vals = [float(v.detach()) for v in losses]
+                    line = ("Step: [%d/%d], time: %.1fs, ds_loss: %.4f, dt_loss: %.4f, g_s_loss: %.4f, g_t_loss: %.4f, lr: %.2e"
+                            % (step, total_step, time.time() - t0, vals[0] + vals[1], vals[2] + vals[3], vals[4], vals[5],
+                               self.g_lr_scher.get_lr()[0]))
+                    for tag, rep in (self.guard_report() or {}).items():
+                        if rep is not None:
+                            line += ", %s |g|: %.3e skipped: %d" % (tag, rep["norm"], rep["skipped"])
+                    print(line)
+                if sample_step and step % sample_step == 0:
+                    self.save_samples(step)
+                if self.model_save_epoch and step % (self.model_save_epoch * steps_per_epoch) == 0:
+                    self.save_models(step)
+        except BaseException:
+            self.close_sheets(quiet=True)          # the loop's exception is the one to report
+            raise
+        self.close_sheets()
+
+    # ---- trainer.py:195-197, 323-334, 389-391: sample sheets (sheets.py)
+    def fixed_inputs(self):
+        """-> (fixed_z [n_class * test_batch_size, z_dim], fixed_label [n_class * test_batch_size]) on the device: the values of
+        trainer.py:195-197, test_batch_size clips per class in class order.  z comes from a private generator seeded with
+        config.sample_seed (the default generator and noise_gen are not touched); drawn once, uploaded once."""
+        if self._fixed is None:
+            gen = torch.Generator().manual_seed(self.sample_seed)
+            z = torch.randn(self.test_batch_size * self.n_class, self.z_dim, generator=gen)
+            label = torch.tensor([i for i in range(self.n_class) for j in range(self.test_batch_size)])
+            self._fixed = (to_device_async(z, self.device), to_device_async(label, self.device))
+        return self._fixed
+
+    @property
+    def sheet_writer(self):
+        """The sheets.SheetWriter the save_* calls submit to (made at first use; `sheet_writer.flush()` waits for the files)."""
+        if self._sheets is None:
+            from .sheets import SheetWriter
+            self._sheets = SheetWriter(max_pending=2)
+        return self._sheets
+
+    def close_sheets(self, quiet=False):
+        """Wait for the pending files and end the writer's thread (a later save_* call starts a new one).  An exception a file
+        hit is raised here, unless quiet."""
+        w, self._sheets = getattr(self, "_sheets", None), None
+        if w is not None:
             try:
-                real_videos, real_labels = next(data_iter)
-            except StopIteration:
-                data_iter = self._new_epoch()
-                real_videos, real_labels = next(data_iter)
-            losses = self.train_step(real_videos, real_labels)
-            if self.log_epoch and step % (self.log_epoch * steps_per_epoch) == 0:
-                vals = [float(v.detach()) for v in losses]
-                line = ("Step: [%d/%d], time: %.1fs, ds_loss: %.4f, dt_loss: %.4f, g_s_loss: %.4f, g_t_loss: %.4f, lr: %.2e"
-                        % (step, total_step, time.time() - t0, vals[0] + vals[1], vals[2] + vals[3], vals[4], vals[5],
-                           self.g_lr_scher.get_lr()[0]))
-                for tag, rep in (self.guard_report() or {}).items():
-                    if rep is not None:
-                        line += ", %s |g|: %.3e skipped: %d" % (tag, rep["norm"], rep["skipped"])
-                print(line)
-            if self.model_save_epoch and step % (self.model_save_epoch * steps_per_epoch) == 0:
-                self.save_models(step)
+                w.close()
+            except Exception:
+                if not quiet:
+                    raise
+
+    def _is_writer(self):
+        return D.world_size() == 1 or torch.distributed.get_rank() == 0
+
+    @torch.no_grad()
+    def save_samples(self, step, fixed_z=None, fixed_label=None, *, chunk=None):
+        """trainer.py:323-334: eval-mode G on the fixed noise, written as sheets under config.sample_path/version.  The clips are
+        generated at most `chunk` at a time (default batch_size), every chunk from the same generator state, and one launch per
+        chunk (sheets.make_sheets on the raw [-1, 1] output: denorm, 8-bit, tiling, RGB interleave) writes straight into the
+        buffer of the whole job, which the writer thread copies out, compresses and writes -- this call waits for none of it.
+        config.sample_layout "frames": `Class_%d_No.%d_Step_%d.png` per clip, its n_frames frames in rows of 8 (the reference's
+        files, with the extension it left out).  "clips": `Step_%d.apng`, one animation frame per time step showing every clip, a
+        row per class, config.sample_fps frames a second.  "both": both.
+        config.sample_use_ema computes with the averaged weights (ema_weights() entered once, config.ema_standing_stats passes).
+        Leaves no trace: weights, spectral-norm u / v, batch-norm statistics and counters are bit-equal before and after (unlike
+        the reference and sample(), whose u / v advance), and no random generator of the run is touched.  In a data-parallel run
+        every rank runs the passes and rank 0 writes."""
+        from .sheets import make_sheets
+        if self.n_cond:
+            raise RuntimeError("a frame-conditional generator (n_cond > 0) continues clips: use save_predictions(step, clips, labels)")
+        if (fixed_z is None) != (fixed_label is None):
+            raise ValueError("give both fixed_z and fixed_label, or neither (fixed_inputs())")
+        if fixed_z is None:
+            z, label = self.fixed_inputs()              # on the device already, in range by construction: no host sync
+            numbering = [(i, j) for i in range(self.n_class) for j in range(self.test_batch_size)]
+        else:
+            z, label = to_device_async(fixed_z, self.device), to_device_async(self._check_labels(fixed_label), self.device)
+            numbering = self._class_and_number(fixed_label)
+        n = z.shape[0]
+        if n < 1 or label.shape[0] != n:
+            raise ValueError(f"fixed_z {tuple(z.shape)} and fixed_label {tuple(label.shape)} must hold the same number of clips")
+        chunk = int(self.batch_size if chunk is None else chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk={chunk}")
+        per_class = self.test_batch_size if n == self.n_class * self.test_batch_size else min(n, 8)
+        do_frames, do_clips = self.sample_layout in ("frames", "both"), self.sample_layout in ("clips", "both")
+        by_clip = by_step = None
+        with self._sampling_weights(self.sample_use_ema, None):
+            frozen = self._g_frozen_tensors()
+            saved = [t.clone() for t in frozen]
+            self.G.eval()
+            try:
+                for lo in range(0, n, chunk):
+                    raw = self.G(z[lo:lo + chunk], label[lo:lo + chunk])          # [b, T, 3, H, W] in [-1, 1]
+                    for t, old in zip(frozen, saved):
+                        t.copy_(old)
+                    if do_frames:
+                        if by_clip is None:
+                            by_clip = torch.empty((n,) + self._sheet_dims(raw.shape[1], raw, 8), dtype=torch.uint8, device=self.device)
+                        make_sheets(raw, layout="frames", row_prefix=True, out=by_clip[lo:lo + raw.shape[0]])
+                    if do_clips:
+                        if by_step is None:
+                            by_step = torch.empty((raw.shape[1],) + self._sheet_dims(n, raw, per_class), dtype=torch.uint8,
+                                                  device=self.device)
+                        make_sheets(raw, layout="clips", nrow=per_class, row_prefix=True, out=by_step, first_slot=lo, total_slots=n,
+                                    fill=lo == 0)
+            finally:
+                self.G.train()
+                for t, old in zip(frozen, saved):
+                    t.copy_(old)
+        if self._is_writer():
+            os.makedirs(self.sample_path, exist_ok=True)
+            if do_frames:
+                names = [os.path.join(self.sample_path, "Class_%d_No.%d_Step_%d.png" % (c, j, step)) for c, j in numbering]
+                self.sheet_writer.submit("png", names, by_clip)
+            if do_clips:
+                self.sheet_writer.submit("apng", os.path.join(self.sample_path, "Step_%d.apng" % step), by_step,
+                                         fps=self.sample_fps, loops=0)
+
+    @staticmethod
+    def _sheet_dims(n_tiles, frames, nrow):
+        from .sheets import sheet_shape
+        Hs, Ws = sheet_shape(n_tiles, frames.shape[-2], frames.shape[-1], nrow)
+        return Hs, 1 + 3 * Ws
+
+    @staticmethod
+    def _class_and_number(labels):
+        """(class, running number within the class) per clip, in clip order: trainer.py:327-332's (i, j) for its fixed labels."""
+        seen, out = {}, []
+        for c in labels.tolist():
+            out.append((c, seen.get(c, 0)))
+            seen[c] = seen.get(c, 0) + 1
+        return out
+
+    @torch.no_grad()
+    def save_predictions(self, step, clips, labels, *, n_samples=1, horizon=None, seed=0):
+        """Comparison sheets of a frame-conditional generator (n_cond = K > 0): clips [B, 3, K + horizon, H, W] in [-1, 1] as the
+        loader delivers them (horizon defaults to n_frames; longer ones are rolled out like rollout()), labels [B] ->
+        `Pred_%d_Step_%d.png` per clip.  Its first row of K + horizon slots holds the real [context | future] frames, row 1 + s
+        the context followed by sampled future s = rollout(cond, labels, horizon, z=z_s), the z of evaluate_prediction(seed=seed)
+        (a private generator).  Every row is written by launches of its own from the views (sheets.make_sheets(first_slot=...)):
+        no concatenated copy.  Leaves no trace, like evaluate_prediction()."""
+        from .sheets import make_sheets
+        K_ = self.n_cond
+        horizon = self.n_frames if horizon is None else int(horizon)
+        self._rollout_args("save_predictions", clips, horizon, (2, K_ + horizon))
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError(f"n_samples={n_samples}")
+        B, L_ = clips.shape[0], K_ + horizon
+        gen = torch.Generator().manual_seed(int(seed))
+        clips = to_device_async(clips, self.device).to(torch.float32)
+        frames = clips.permute(0, 2, 1, 3, 4)                          # [B, K + horizon, 3, H, W], a view
+        ctx_view, cond = frames[:, :K_], frames[:, :K_].contiguous()
+        labels_d = to_device_async(self._check_labels(labels), self.device)
+        zs = to_device_async(torch.stack([torch.randn(B, self.z_dim, generator=gen) for _ in range(n_samples)]), self.device)
+        total = (1 + n_samples) * L_
+        out = torch.empty((B,) + self._sheet_dims(total, frames, L_), dtype=torch.uint8, device=self.device)
+        make_sheets(frames, nrow=L_, row_prefix=True, out=out, total_slots=total)                  # row 0, borders, every other slot
+        frozen = self._g_frozen_tensors()
+        saved = [t.clone() for t in frozen]
+        self.G.eval()
+        try:
+            for s in range(n_samples):
+                z = zs[s]
+                raw = self._rollout_raw(cond, labels_d, horizon, lambda: z)
+                for t, old in zip(frozen, saved):
+                    t.copy_(old)
+                make_sheets(ctx_view, nrow=L_, row_prefix=True, out=out, first_slot=(1 + s) * L_, total_slots=total, fill=False)
+                make_sheets(raw, nrow=L_, row_prefix=True, out=out, first_slot=(1 + s) * L_ + K_, total_slots=total, fill=False)
+        finally:
+            self.G.train()
+            for t, old in zip(frozen, saved):
+                t.copy_(old)
+        if self._is_writer():
+            os.makedirs(self.sample_path, exist_ok=True)
+            self.sheet_writer.submit("png", [os.path.join(self.sample_path, "Pred_%d_Step_%d.png" % (b, step)) for b in range(B)], out)
+
+    @torch.no_grad()
+    def save_real(self, real_videos):
+        """trainer.py:389-391: the loader's clips [B, 3, T, H, W] in [-1, 1] -> `real_%d.png` per clip, the sheet save_samples
+        writes for a generated one (read through the clip's strides: no permuted copy)."""
+        from .sheets import make_sheets
+        if real_videos.dim() != 5 or real_videos.shape[1] != 3:
+            raise ValueError(f"real_videos {tuple(real_videos.shape)} must be [B, 3, T, H, W]")
+        clips = to_device_async(real_videos, self.device).to(torch.float32)
+        out = make_sheets(clips.permute(0, 2, 1, 3, 4), row_prefix=True)
+        if self._is_writer():
+            os.makedirs(self.sample_path, exist_ok=True)
+            self.sheet_writer.submit("png", [os.path.join(self.sample_path, "real_%d.png" % b) for b in range(out.shape[0])], out)
 
     # ---- the averaged generator weights
     def _ema_on(self):
@@ -563,8 +766,8 @@ class Trainer(object):
             return torch.randn(batch, self.z_dim, generator=self.noise_gen)
         return truncated_z(batch, self.z_dim, truncation, generator=self.noise_gen)
 
-    # ---- trainer.py:323-334: the sampling path (eval-mode G on fixed z / labels, BN running statistics), without
-    # the image-file side (torchvision save_image / tensorboard are host plumbing)
+    # ---- trainer.py:323-334: the sampling path (eval-mode G on fixed z / labels, BN running statistics); the image files are
+    # save_samples() above (tensorboard stays out)
     @torch.no_grad()
     def sample(self, fixed_z, fixed_label, *, use_ema=False, standing_stats=None, truncation=None):
         """-> denorm(G(fixed_z, fixed_label)) [B, T, 3, H, W] in [0, 1]; G is put back in train mode, like the reference.

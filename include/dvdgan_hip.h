@@ -607,6 +607,46 @@ int dvd_clip_gather(const unsigned char* blob, long long blob_bytes, const long 
                     const int* tables, long long table_ints, float* dst, long long B, int T, int S, float norm_value,
                     const float* mean_std, void* stream);
 
+/* Sample sheets (sheets.make_sheets, Trainer.save_samples; trainer.py:323-334's save_image(denorm(clip)) = torchvision's make_grid
+ * over the frames of a clip, and the 8-bit quantisation of save_image; additions: the ABI version stays 13).  One launch reads fp32
+ * frames and writes 8-bit interleaved RGB sheets, ready for a PNG's deflate.
+ * `src`: device fp32 seen as [n_sheets][n_tiles][3][H][W]: the H x W planes contiguous, the sheet, tile and channel strides given
+ * in ELEMENTS (>= 0; channel stride >= H * W).  A generated batch [B][T][3][H][W] gives one sheet per clip (tiles = its frames) or,
+ * with the first two strides exchanged, one sheet per time step (tiles = the clips); a loader clip [B][3][T][H][W] is served through
+ * its strides as well.
+ * Geometry: torchvision's make_grid(nrow, padding, pad_value) for a sheet of `total_slots` slots:
+ *   xmaps = min(nrow, total_slots), ymaps = ceil(total_slots / xmaps), Hs = ymaps (H + padding) + padding,
+ *   Ws = xmaps (W + padding) + padding, slot k has its top-left pixel at row (k / xmaps)(H + padding) + padding, column
+ *   (k % xmaps)(W + padding) + padding; borders and the empty slots of the last row hold pad_value.  One deviation: a single
+ *   tile keeps its border (torchvision returns a lone image bare).
+ * The launch fills slots [first_slot, first_slot + n_tiles) with its tiles.  With DVD_SHEET_FILL it also writes every other byte of
+ * the sheets (borders, all other slots, the prefix bytes); without, it writes its own tiles' pixels and nothing else -- so launches
+ * on one stream compose a sheet from several sources.
+ * Value: with DVD_SHEET_SIGNED x = (v + 1) / 2, else x = v; then x = clamp(x, 0, 1), q = clamp(x * 255 + 0.5, 0, 255), byte = q
+ * truncated -- every operation rounded on its own in fp32 (no fused multiply-add), the bytes of
+ * `x.add(1).div(2).clamp_(0, 1).mul(255).add_(0.5).clamp_(0, 255).to(uint8)`.  +inf -> 255, -inf -> 0, NaN -> 0.  pad_value is
+ * quantised as a [0, 1] value.
+ * `dst`: device uint8 [n_sheets][Hs][row_prefix + 3 Ws], tight rows, any alignment.  row_prefix = 1 starts every row with a zero
+ * byte (PNG filter type "None"): a sheet is then the input of the IDAT's deflate as it stands.
+ * Deterministic: every byte has one writer, no atomics.  All checks come before any launch:
+ * DVD_E_ARG: a null pointer, n_sheets / n_tiles / total_slots / nrow < 1, first_slot < 0, first_slot + n_tiles > total_slots,
+ *   padding outside [0, DVD_SHEET_MAX_PADDING], row_prefix not 0 / 1, unknown flag bits, a negative stride, a channel stride
+ *   below H * W.
+ * DVD_E_SHAPE: H or W outside [1, DVD_SHEET_MAX_TILE], Hs or Ws above DVD_SHEET_MAX_SIDE, a source byte offset or the destination
+ *   size beyond 2^63 - 1, n_sheets * Hs >= 2^31.
+ * dvd_sample_sheet_shape (no GPU needed) returns Hs, Ws and the bytes of ONE sheet, Hs * (row_prefix + 3 Ws), with the same
+ * refusals for the arguments it takes. */
+#define DVD_SHEET_FILL 1
+#define DVD_SHEET_SIGNED 2
+#define DVD_SHEET_MAX_TILE 4096
+#define DVD_SHEET_MAX_SIDE 16384
+#define DVD_SHEET_MAX_PADDING 64
+int dvd_sample_sheet_shape(int total_slots, int H, int W, int nrow, int padding, int row_prefix, int* Hs, int* Ws,
+                           long long* sheet_bytes);
+int dvd_sample_sheet(const float* src, long long s_sheet, long long s_tile, long long s_chan, long long n_sheets, int n_tiles,
+                     int H, int W, int first_slot, int total_slots, int nrow, int padding, float pad_value, int row_prefix,
+                     int flags, unsigned char* dst, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
