@@ -24,7 +24,6 @@ Split of work there:
   device, per step (`ClipStore.gather`, kernel dvd_clip_gather): crop, the two integer resize passes, flip, normalise and layout
       in one launch.  The bytes equal the host reader's: PIL's 8-bit resize is integer arithmetic on those tables.
 """
-import ctypes as C
 import json
 import math
 import os
@@ -169,8 +168,8 @@ def clips_to_device(clips, flips, device, norm_value=255.0, mean=(0.5, 0.5, 0.5)
     assert ch == 3 and clips.dtype == torch.uint8
     out = torch.empty(B, 3, T, S1, S2, dtype=torch.float32, device=device)
     ms = torch.tensor(list(mean) + list(std), dtype=torch.float32, device=device)
-    L.check(L.lib().dvd_clip_to_tensor(L.ptr(clips), L.ptr(flips), L.ptr(out), C.c_longlong(B), T, S1, S2,
-                                       C.c_float(norm_value), L.ptr(ms), L.stream()))
+    L.check(L.lib().dvd_clip_to_tensor(L.ptr(clips), L.ptr(flips), L.ptr(out), B, T, S1, S2, float(norm_value), L.ptr(ms),
+                                       L.stream()))
     return out
 
 

@@ -510,7 +510,7 @@ class ConvGRULayer(Function):
         states = _gru_states(x, T, B, hid, infer)
         h32 = torch.empty(2, M, hid, dtype=torch.float32, device=dev) if dtype != torch.float32 else None
         lib = L.lib()
-        nsplit = lambda cout, c: min(lib.dvd_conv_pick_nsplit(L.dt(x), C.c_longlong(M), cout, c, k * k), GRU_NS_CAP or 1 << 30)
+        nsplit = lambda cout, c: min(lib.dvd_conv_pick_nsplit(L.dt(x), M, cout, c, k * k), GRU_NS_CAP or 1 << 30)
         ws_n = lib.dvd_convgru_ws_floats(L.dt(x), B, S1, S2, hid, k)
         ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
         d = L.GruDesc()
@@ -543,7 +543,7 @@ class ConvGRULayer(Function):
         carry = torch.empty(M, hid, dtype=torch.float32, device=dev)
         ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
         lib = L.lib()
-        nsplit = lambda cout, c: min(lib.dvd_conv_pick_nsplit(L.dt(x), C.c_longlong(M), cout, c, k * k), GRU_NS_CAP or 1 << 30)
+        nsplit = lambda cout, c: min(lib.dvd_conv_pick_nsplit(L.dt(x), M, cout, c, k * k), GRU_NS_CAP or 1 << 30)
         d = L.GruDesc()
         dh0_32 = _gru_desc_backward(d, x, T, B, hid, k, (h_all, u_all, r_all, o_all, hr_all), h0, pur, po, dh, dg, carry,
                                     ctx.needs_input_grad[9])
@@ -733,15 +733,14 @@ class SelfAttention2d(Function):
             y, att = torch.empty_like(x), torch.empty_like(x)
             lse = torch.empty(F_, N, dtype=torch.float32, device=x.device)
             L.check(lib.dvd_attention_mfma_forward(L.ptr(qkv), qkv.shape[-1], L.ptr(x), C_real, L.ptr(gamma), L.ptr(y),
-                                                   L.ptr(att), L.ptr(lse), C.c_longlong(F_), N, L.stream()))
+                                                   L.ptr(att), L.ptr(lse), F_, N, L.stream()))
             ctx.save_for_backward(qkv, gamma, att, lse)
             return y
         y = torch.zeros_like(x) if x.shape[-1] != C_real else torch.empty_like(x)
         att = torch.zeros_like(x)
         A = torch.empty(F_, N, N, dtype=torch.float32, device=x.device)
         L.check(lib.dvd_attention_forward(L.dt(x), L.ptr(qkv), qkv.shape[-1], dq, koff, voff, L.ptr(x), x.shape[-1],
-                                          C_real, L.ptr(gamma), L.ptr(y), L.ptr(att), L.ptr(A), C.c_longlong(F_), N,
-                                          L.stream()))
+                                          C_real, L.ptr(gamma), L.ptr(y), L.ptr(att), L.ptr(A), F_, N, L.stream()))
         ctx.save_for_backward(qkv, gamma, att, A)
         return y
 
@@ -757,14 +756,13 @@ class SelfAttention2d(Function):
             dqkv = torch.empty_like(qkv) if qkv.shape[-1] == 32 + C_real else torch.zeros_like(qkv)
             D = torch.empty_like(A)
             L.check(L.lib().dvd_attention_mfma_backward(L.ptr(qkv), qkv.shape[-1], L.ptr(dy), C_real, L.ptr(gamma), L.ptr(att),
-                                                        L.ptr(A), L.ptr(D), L.ptr(dqkv), L.ptr(dgamma), C.c_longlong(F_), N,
-                                                        L.stream()))
+                                                        L.ptr(A), L.ptr(D), L.ptr(dqkv), L.ptr(dgamma), F_, N, L.stream()))
             return dy, dqkv, (None if direct else dgamma), None, None
         dqkv = torch.zeros_like(qkv)
         dS = torch.empty_like(A)
         L.check(L.lib().dvd_attention_backward(L.dt(dy), L.ptr(qkv), qkv.shape[-1], dq, koff, voff, L.ptr(dy),
                                                dy.shape[-1], C_real, L.ptr(gamma), L.ptr(att), L.ptr(A), L.ptr(dS),
-                                               L.ptr(dqkv), L.ptr(dgamma), C.c_longlong(F_), N, L.stream()))
+                                               L.ptr(dqkv), L.ptr(dgamma), F_, N, L.stream()))
         return dy, dqkv, (None if direct else dgamma), None, None
 
 
@@ -775,7 +773,7 @@ class MaxPool3d(Function):
     def forward(ctx, x):
         F_, T, H, W, ld = x.shape
         y = torch.empty(F_, T // 2, H // 2, W // 2, ld, dtype=x.dtype, device=x.device)
-        L.check(L.lib().dvd_maxpool3d(L.dt(x), L.ptr(x), L.ptr(y), C.c_longlong(F_), T // 2, H // 2, W // 2, ld, L.stream()))
+        L.check(L.lib().dvd_maxpool3d(L.dt(x), L.ptr(x), L.ptr(y), F_, T // 2, H // 2, W // 2, ld, L.stream()))
         ctx.save_for_backward(x)
         return y
 
@@ -785,8 +783,8 @@ class MaxPool3d(Function):
         dy = dy.contiguous()
         F_, T, H, W, ld = x.shape
         dx = torch.empty_like(x)
-        L.check(L.lib().dvd_maxpool3d_backward(L.dt(x), L.ptr(x), L.ptr(dy), L.ptr(dx), C.c_longlong(F_), T // 2, H // 2,
-                                               W // 2, ld, L.stream()))
+        L.check(L.lib().dvd_maxpool3d_backward(L.dt(x), L.ptr(x), L.ptr(dy), L.ptr(dx), F_, T // 2, H // 2, W // 2, ld,
+                                               L.stream()))
         return dx
 
 
@@ -807,7 +805,7 @@ class SelfAttentionKV(Function):
         A = torch.empty(F_, N, Nk, dtype=torch.float32, device=x.device)
         L.check(L.lib().dvd_attention_kv_forward(L.dt(x), L.ptr(qkv), qkv.shape[-1], dq, L.ptr(kv), kv.shape[-1], koff, voff,
                                                  L.ptr(x), x.shape[-1], C_real, L.ptr(gamma), L.ptr(y), L.ptr(att), L.ptr(A),
-                                                 C.c_longlong(F_), N, Nk, L.stream()))
+                                                 F_, N, Nk, L.stream()))
         ctx.save_for_backward(qkv, kv, gamma, att, A)
         ctx.meta = (dq, C_real, koff, voff, N, Nk)
         return y
@@ -824,8 +822,7 @@ class SelfAttentionKV(Function):
         dgamma = torch.zeros(1, dtype=torch.float32, device=dy.device)
         L.check(L.lib().dvd_attention_kv_backward(L.dt(dy), L.ptr(qkv), qkv.shape[-1], dq, L.ptr(kv), kv.shape[-1], koff,
                                                   voff, L.ptr(dy), dy.shape[-1], C_real, L.ptr(gamma), L.ptr(att), L.ptr(A),
-                                                  L.ptr(dS), L.ptr(dqkv), L.ptr(dkv), L.ptr(dgamma), C.c_longlong(F_), N, Nk,
-                                                  L.stream()))
+                                                  L.ptr(dS), L.ptr(dqkv), L.ptr(dkv), L.ptr(dgamma), F_, N, Nk, L.stream()))
         return dy, dqkv, dkv, dgamma, None, None
 
 
@@ -848,7 +845,7 @@ class SeparableAttnCellFn(Function):
         y = torch.zeros_like(x) if ldx != C_real else torch.empty_like(x)
         L.check(L.lib().dvd_sepattn_forward(L.dt(x), L.ptr(qkv), qkv.shape[-1], dq, koff, voff, L.ptr(x), ldx, C_real,
                                             L.ptr(gamma), L.ptr(y), L.ptr(Qf), L.ptr(Kp), L.ptr(Vp), L.ptr(ksel), L.ptr(vsel),
-                                            L.ptr(att), C.c_longlong(B), T, W, H, axis, L.stream()))
+                                            L.ptr(att), B, T, W, H, axis, L.stream()))
         ctx.save_for_backward(gamma, Qf, Kp, Vp, ksel, vsel, att)
         ctx.meta = (B, T, W, H, ldx, qkv.shape[-1], dq, C_real, koff, voff, axis, qkv.dtype)
         return y
@@ -867,8 +864,8 @@ class SeparableAttnCellFn(Function):
         dgamma = torch.zeros(1, dtype=torch.float32, device=dev)
         L.check(L.lib().dvd_sepattn_backward(L.dt(dy), L.ptr(dy), ldx, C_real, dq, L.ptr(gamma), L.ptr(Qf), L.ptr(Kp), L.ptr(Vp),
                                              L.ptr(ksel), L.ptr(vsel), L.ptr(att), L.ptr(dO), L.ptr(dS), L.ptr(dQf), L.ptr(dKp),
-                                             L.ptr(dVp), L.ptr(dqkv), ldq, koff, voff, L.ptr(dgamma), C.c_longlong(B), T, W, H,
-                                             axis, L.stream()))
+                                             L.ptr(dVp), L.ptr(dqkv), ldq, koff, voff, L.ptr(dgamma), B, T, W, H, axis,
+                                             L.stream()))
         return dy, dqkv, dgamma, None, None, None
 
 
@@ -882,13 +879,12 @@ class ProjectionHead(Function):
         P = feat.numel() // (F_ * feat.shape[-1])
         lib = L.lib()
         hsum = torch.empty(F_, C_real, dtype=torch.float32, device=feat.device)
-        L.check(lib.dvd_relu_spatial_sum(L.dt(feat), L.ptr(feat), L.ptr(hsum), C.c_longlong(F_), P, C_real,
-                                         feat.shape[-1], L.stream()))
+        L.check(lib.dvd_relu_spatial_sum(L.dt(feat), L.ptr(feat), L.ptr(hsum), F_, P, C_real, feat.shape[-1], L.stream()))
         s_l = K.sn_power_iter(w_lin, *sn_lin)
         s_e = K.sn_power_iter(w_emb, *sn_emb)
         out = torch.empty(F_, dtype=torch.float32, device=feat.device)
         L.check(lib.dvd_proj_head_forward(L.ptr(hsum), L.ptr(w_lin), L.ptr(s_l), L.ptr(b_lin), L.ptr(w_emb), L.ptr(s_e),
-                                          L.ptr(cls32), L.ptr(out), C.c_longlong(F_), C_real, L.stream()))
+                                          L.ptr(cls32), L.ptr(out), F_, C_real, L.stream()))
         ctx.save_for_backward(feat, hsum, w_lin, w_emb, cls32, s_l, s_e)
         ctx.sn = (sn_lin, sn_emb)
         ctx.params = (w_lin, b_lin, w_emb)
@@ -909,13 +905,13 @@ class ProjectionHead(Function):
         g_emb = torch.zeros_like(w_emb) if need_w else None
         g_b = (ctx.params[1].grad if direct else torch.zeros(1, dtype=torch.float32, device=feat.device)) if need_w else None
         L.check(lib.dvd_proj_head_backward(L.ptr(dout), L.ptr(hsum), L.ptr(w_lin), L.ptr(s_l), L.ptr(w_emb), L.ptr(s_e),
-                                           L.ptr(cls32), L.ptr(dh), L.ptr(g_lin), L.ptr(g_emb), L.ptr(g_b),
-                                           C.c_longlong(F_), C_real, L.stream()))
+                                           L.ptr(cls32), L.ptr(dh), L.ptr(g_lin), L.ptr(g_emb), L.ptr(g_b), F_, C_real,
+                                           L.stream()))
         dfeat = None
         if ctx.needs_input_grad[0]:
             dfeat = torch.empty_like(feat)
-            L.check(lib.dvd_relu_spatial_sum_backward(L.dt(feat), L.ptr(dh), L.ptr(feat), L.ptr(dfeat), C.c_longlong(F_),
-                                                      P, C_real, feat.shape[-1], L.stream()))
+            L.check(lib.dvd_relu_spatial_sum_backward(L.dt(feat), L.ptr(dh), L.ptr(feat), L.ptr(dfeat), F_, P, C_real,
+                                                      feat.shape[-1], L.stream()))
         dwl = dwe = None
         if direct:                 # spectral-norm backward adds straight into the persistent .grad buffers
             K.sn_backward(g_lin, w_lin, sn_lin[0], sn_lin[1], s_l, out=ctx.params[0].grad)
@@ -935,8 +931,8 @@ class AdvLoss(Function):
         out = out.contiguous()
         loss = torch.zeros(1, dtype=torch.float32, device=out.device)
         dout = torch.empty_like(out)
-        L.check(L.lib().dvd_adv_loss(L.ptr(out), C.c_longlong(out.numel()), int(hinge), int(real_flag), L.ptr(loss),
-                                     L.ptr(dout), C.c_float(1.0), L.stream()))
+        L.check(L.lib().dvd_adv_loss(L.ptr(out), out.numel(), int(hinge), int(real_flag), L.ptr(loss), L.ptr(dout), 1.0,
+                                     L.stream()))
         ctx.save_for_backward(dout)
         return loss.view(())
 

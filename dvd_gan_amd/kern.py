@@ -9,6 +9,8 @@ import os
 import torch
 
 from . import lib as L
+from .lib import (GUARD_CH, GUARD_STATE, METRICS_QUANTIZE, METRICS_SIGNED, ORTHO_COLS, ORTHO_H, ORTHO_OFF, ORTHO_W, SHEET_FILL,
+                  SHEET_SIGNED)       # (public names of this module; the values live with the other header constants)
 
 
 def pad8(c):
@@ -32,8 +34,8 @@ def to_cl(x, dtype, swap=None):
         P *= s
     out = torch.empty((F_,) + sp + (pad8(Cc),), dtype=dtype, device=x.device)
     A, B = swap if swap else (F_, 1)
-    L.check(L.lib().dvd_to_channels_last(L.dt(out), L.ptr(x), L.ptr(out), C.c_longlong(F_), Cc, C.c_longlong(P),
-                                         pad8(Cc), A, B, 1 if swap else 0, L.stream()))
+    L.check(L.lib().dvd_to_channels_last(L.dt(out), L.ptr(x), L.ptr(out), F_, Cc, P, pad8(Cc), A, B, 1 if swap else 0,
+                                         L.stream()))
     return out
 
 
@@ -46,14 +48,14 @@ def from_cl(t, channels, swap=None):
         P *= s
     out = torch.empty((F_, channels) + sp, dtype=torch.float32, device=t.device)
     A, B = swap if swap else (F_, 1)
-    L.check(L.lib().dvd_from_channels_last(L.dt(t), L.ptr(t), L.ptr(out), C.c_longlong(F_), channels,
-                                           C.c_longlong(P), Cp, A, B, 1 if swap else 0, L.stream()))
+    L.check(L.lib().dvd_from_channels_last(L.dt(t), L.ptr(t), L.ptr(out), F_, channels, P, Cp, A, B, 1 if swap else 0,
+                                           L.stream()))
     return out
 
 
 def convert(src, dtype):
     out = torch.empty(src.shape, dtype=dtype, device=src.device)
-    L.check(L.lib().dvd_convert(L.dt(src), L.ptr(src), L.dt(out), L.ptr(out), C.c_longlong(src.numel()), L.stream()))
+    L.check(L.lib().dvd_convert(L.dt(src), L.ptr(src), L.dt(out), L.ptr(out), src.numel(), L.stream()))
     return out
 
 
@@ -146,11 +148,10 @@ class PackBatch:
         dt_ = L.BF16 if self.dtype == torch.bfloat16 else L.F32
         if not PACK_BATCH:                # A/B aid: one launch per item, as before round 6
             for it, *_ in self.fills:
-                vp = C.c_void_p
-                L.check(L.lib().dvd_pack_conv_weight(dt_, vp(it.w), vp(it.sigma), it.Cout, it.Cin, it.ntaps, it.Cip, it.co_off, it.co_tot_f,
-                                                     it.co_tot_d, vp(it.wf), vp(it.wd), it.kt, it.kh, it.kw, it.ci_off, it.ci_tot, L.stream()))
+                L.check(L.lib().dvd_pack_conv_weight(dt_, it.w, it.sigma, it.Cout, it.Cin, it.ntaps, it.Cip, it.co_off, it.co_tot_f,
+                                                     it.co_tot_d, it.wf, it.wd, it.kt, it.kh, it.kw, it.ci_off, it.ci_tot, L.stream()))
             for it, *_ in self.frags:
-                L.check(L.lib().dvd_conv_fragment_major(L.BF16, C.c_void_p(it.w), C.c_void_p(it.wq), it.ntaps, it.Cout, it.C, L.stream()))
+                L.check(L.lib().dvd_conv_fragment_major(L.BF16, it.w, it.wq, it.ntaps, it.Cout, it.C, L.stream()))
         else:
             if self.fills:
                 arr = (L.PackItem * len(self.fills))(*[f[0] for f in self.fills])
@@ -310,14 +311,6 @@ def conv_wgrad(x, dy, dw, ksize, cout, cin_real, *, up2=False, relu_in=False, ms
 
 
 # ------------------------------------------------------------------ pointwise wrappers
-def _ll(v):
-    return C.c_longlong(int(v))
-
-
-def _f(v):
-    return C.c_float(float(v))
-
-
 def bn_stats(x, C_real, training, eps, momentum, run_mean, run_var, replicas=None, sums=None):
     """-> (mean, rstd) fp32 [C_real]; updates the running buffers in training mode.
     sums: optional PERSISTENT zeroed fp64 workspace [BN_NREP * 2 * C_real] of the caller -- dvd_bn_finalize leaves it zeroed
@@ -337,11 +330,11 @@ def bn_stats(x, C_real, training, eps, momentum, run_mean, run_var, replicas=Non
                 sums = torch.zeros(L.BN_NREP * 2 * C_real, dtype=torch.float64, device=x.device)
             if EXP_CBN & 1:               # timing experiment (wrong statistics): the pass over x reads 4096 rows only
                 rows = min(rows, 4096)
-            L.check(L.lib().dvd_bn_stats(L.dt(x), L.ptr(x), _ll(rows), C_real, ld, L.ptr(sums), L.stream()))
+            L.check(L.lib().dvd_bn_stats(L.dt(x), L.ptr(x), rows, C_real, ld, L.ptr(sums), L.stream()))
             if replicas is not None:
                 replicas[1](sums)
                 rows *= replicas[0]
-        L.check(L.lib().dvd_bn_finalize(L.ptr(sums), _ll(rows), C_real, _f(eps), _f(momentum), int(training),
+        L.check(L.lib().dvd_bn_finalize(L.ptr(sums), rows, C_real, eps, momentum, int(training),
                                         L.ptr(mean), L.ptr(rstd), L.ptr(run_mean), L.ptr(run_var), int(keep), L.stream()))
     except Exception:
         if keep:
@@ -354,7 +347,7 @@ def cbn_apply(x, C_real, mean, rstd, gb, samp, relu):
     y = torch.empty_like(x)
     frames = x.shape[0]
     P = x.numel() // (frames * x.shape[-1])
-    L.check(L.lib().dvd_cbn_apply(L.dt(x), L.ptr(x), L.ptr(y), _ll(frames), P, C_real, x.shape[-1], L.ptr(mean),
+    L.check(L.lib().dvd_cbn_apply(L.dt(x), L.ptr(x), L.ptr(y), frames, P, C_real, x.shape[-1], L.ptr(mean),
                                   L.ptr(rstd), L.ptr(gb), L.ptr(samp), int(relu), L.stream()))
     return y
 
@@ -368,27 +361,27 @@ def cbn_backward(g, a, x, C_real, mean, rstd, gb, samp, relu, replicas=None):
     B = gb.shape[0]
     dgb = torch.zeros_like(gb)
     s12 = torch.empty(2 * C_real, dtype=torch.float32, device=x.device)
-    part = torch.empty(L.lib().dvd_cbn_backward_ws_floats(_ll(frames), P, C_real), dtype=torch.float32, device=x.device)   # fixed-order dgb
+    part = torch.empty(L.lib().dvd_cbn_backward_ws_floats(frames, P, C_real), dtype=torch.float32, device=x.device)   # fixed-order dgb
     if EXP_CBN & 2 and replicas is None:      # timing experiment (wrong sums): the reduce pass reads two frames only
-        L.check(L.lib().dvd_cbn_backward_reduce(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), _ll(min(frames, 2)), P, C_real, x.shape[-1],
+        L.check(L.lib().dvd_cbn_backward_reduce(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), min(frames, 2), P, C_real, x.shape[-1],
                                                 L.ptr(mean), L.ptr(rstd), L.ptr(gb), L.ptr(samp), B, L.ptr(dgb), L.ptr(s12),
                                                 int(relu), L.ptr(part), L.stream()))
-        L.check(L.lib().dvd_cbn_backward_apply(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), L.ptr(dx), _ll(frames), P, C_real,
+        L.check(L.lib().dvd_cbn_backward_apply(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), L.ptr(dx), frames, P, C_real,
                                                x.shape[-1], L.ptr(mean), L.ptr(rstd), L.ptr(gb), L.ptr(samp), L.ptr(s12),
-                                               _ll(frames * P), int(relu), L.stream()))
+                                               frames * P, int(relu), L.stream()))
         return dx, dgb
     if replicas is None:
-        L.check(L.lib().dvd_cbn_backward(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), L.ptr(dx), _ll(frames), P, C_real,
+        L.check(L.lib().dvd_cbn_backward(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), L.ptr(dx), frames, P, C_real,
                                          x.shape[-1], L.ptr(mean), L.ptr(rstd), L.ptr(gb), L.ptr(samp), B, L.ptr(dgb),
                                          L.ptr(s12), int(relu), L.ptr(part), L.stream()))
         return dx, dgb
-    L.check(L.lib().dvd_cbn_backward_reduce(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), _ll(frames), P, C_real, x.shape[-1],
+    L.check(L.lib().dvd_cbn_backward_reduce(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), frames, P, C_real, x.shape[-1],
                                             L.ptr(mean), L.ptr(rstd), L.ptr(gb), L.ptr(samp), B, L.ptr(dgb), L.ptr(s12),
                                             int(relu), L.ptr(part), L.stream()))
     replicas[1](s12)
-    L.check(L.lib().dvd_cbn_backward_apply(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), L.ptr(dx), _ll(frames), P, C_real,
+    L.check(L.lib().dvd_cbn_backward_apply(L.dt(x), L.ptr(g), L.ptr(a), L.ptr(x), L.ptr(dx), frames, P, C_real,
                                            x.shape[-1], L.ptr(mean), L.ptr(rstd), L.ptr(gb), L.ptr(samp), L.ptr(s12),
-                                           _ll(frames * P * replicas[0]), int(relu), L.stream()))
+                                           frames * P * replicas[0], int(relu), L.stream()))
     return dx, dgb
 
 
@@ -407,10 +400,10 @@ def pool(x, pt=1, scale=None, mask=None):
     y = torch.empty(shape, dtype=x.dtype, device=x.device)
     if mask is not None:
         assert mask.shape == y.shape and mask.dtype == y.dtype and not ((H | W) & 1)
-        L.check(L.lib().dvd_pool_masked(L.dt(x), L.ptr(x), L.ptr(mask), L.ptr(y), _ll(F_), To, Ho, Wo, x.shape[-1], pt, _f(scale),
+        L.check(L.lib().dvd_pool_masked(L.dt(x), L.ptr(x), L.ptr(mask), L.ptr(y), F_, To, Ho, Wo, x.shape[-1], pt, scale,
                                         L.stream()))
         return y
-    L.check(L.lib().dvd_pool(L.dt(x), L.ptr(x), L.ptr(y), _ll(F_), To, Ho, Wo, H, W, x.shape[-1], pt, _f(scale), L.stream()))
+    L.check(L.lib().dvd_pool(L.dt(x), L.ptr(x), L.ptr(y), F_, To, Ho, Wo, H, W, x.shape[-1], pt, scale, L.stream()))
     return y
 
 
@@ -425,7 +418,7 @@ def unpool(x, pt=1, scale=None, out_hw=None):
     scale = (1.0 / (4 * pt)) if scale is None else scale
     shape = (F_, To, Ho, Wo, x.shape[-1]) if x.dim() == 5 else (F_, Ho, Wo, x.shape[-1])
     y = torch.empty(shape, dtype=x.dtype, device=x.device)
-    L.check(L.lib().dvd_unpool(L.dt(x), L.ptr(x), L.ptr(y), _ll(F_), To, Ho, Wo, x.shape[-1], pt, _f(scale), L.stream()))
+    L.check(L.lib().dvd_unpool(L.dt(x), L.ptr(x), L.ptr(y), F_, To, Ho, Wo, x.shape[-1], pt, scale, L.stream()))
     return y
 
 
@@ -433,25 +426,25 @@ def colsum(x, C_real, out=None):
     ld = x.shape[-1]
     if out is None:
         out = torch.zeros(C_real, dtype=torch.float32, device=x.device)
-    L.check(L.lib().dvd_colsum(L.dt(x), L.ptr(x), _ll(x.numel() // ld), C_real, ld, L.ptr(out), L.stream()))
+    L.check(L.lib().dvd_colsum(L.dt(x), L.ptr(x), x.numel() // ld, C_real, ld, L.ptr(out), L.stream()))
     return out
 
 
 def add(a, b):
     out = torch.empty_like(a)
-    L.check(L.lib().dvd_add(L.dt(a), L.ptr(a), L.ptr(b), L.ptr(out), _ll(a.numel()), L.stream()))
+    L.check(L.lib().dvd_add(L.dt(a), L.ptr(a), L.ptr(b), L.ptr(out), a.numel(), L.stream()))
     return out
 
 
 def sum_leading(x):
     out = torch.empty(x.shape[1:], dtype=x.dtype, device=x.device)
-    L.check(L.lib().dvd_sum_leading(L.dt(x), L.ptr(x), L.ptr(out), x.shape[0], _ll(out.numel()), L.stream()))
+    L.check(L.lib().dvd_sum_leading(L.dt(x), L.ptr(x), L.ptr(out), x.shape[0], out.numel(), L.stream()))
     return out
 
 
 def act_backward(dy, y, act):
     dx = torch.empty_like(dy)
-    L.check(L.lib().dvd_act_backward(L.dt(dy), L.ptr(dy), L.ptr(y), L.ptr(dx), _ll(dy.numel()), act, L.stream()))
+    L.check(L.lib().dvd_act_backward(L.dt(dy), L.ptr(dy), L.ptr(y), L.ptr(dx), dy.numel(), act, L.stream()))
     return dx
 
 
@@ -485,7 +478,7 @@ def row_copy(src, idx, nrows_out, L_, scatter, out=None):
     """gather: out[r] = src[idx[r]] ; scatter: out[idx[r]] = src[r] (out pre-zeroed, nrows_out rows)."""
     if out is None:
         out = (torch.zeros if scatter else torch.empty)(nrows_out, L_, dtype=torch.float32, device=src.device)
-    L.check(L.lib().dvd_row_copy(L.ptr(src), L.ptr(out), L.ptr(idx), _ll(idx.numel()), _ll(L_), int(scatter), L.stream()))
+    L.check(L.lib().dvd_row_copy(L.ptr(src), L.ptr(out), L.ptr(idx), idx.numel(), L_, int(scatter), L.stream()))
     return out
 
 
@@ -533,23 +526,21 @@ def linear_backward(dout, inp, W, need_in, need_w, has_bias, dW=None, db=None):
 def embedding_backward(dout, idx, nrows, dW=None):
     if dW is None:
         dW = torch.zeros(nrows, dout.shape[1], dtype=torch.float32, device=dout.device)
-    L.check(L.lib().dvd_embedding_backward(L.ptr(dout), L.ptr(idx), L.ptr(dW), _ll(dout.shape[0]), dout.shape[1], L.stream()))
+    L.check(L.lib().dvd_embedding_backward(L.ptr(dout), L.ptr(idx), L.ptr(dW), dout.shape[0], dout.shape[1], L.stream()))
     return dW
 
 
 def adam_step(p, g, m, v, lr, b1, b2, eps, step):
-    L.check(L.lib().dvd_adam_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), _ll(p.numel()), _f(lr), _f(b1), _f(b2),
-                                  _f(eps), int(step), L.stream()))
+    L.check(L.lib().dvd_adam_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), float(lr), b1, b2, eps, int(step),
+                                  L.stream()))
 
 
 def adam_ema_step(p, g, m, v, ema, lr, b1, b2, eps, step, decay):
     """adam_step and ema = decay * ema + (1 - decay) * p_new in one launch."""
-    L.check(L.lib().dvd_adam_ema_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), _ll(p.numel()), _f(lr), _f(b1),
-                                      _f(b2), _f(eps), int(step), _f(decay), L.stream()))
+    L.check(L.lib().dvd_adam_ema_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), p.numel(), float(lr), b1, b2, eps,
+                                      int(step), float(decay), L.stream()))
 
 
-GUARD_CH = 16384                                 # DVD_GUARD_CH of include/dvdgan_hip.h: elements per workgroup of the norm pass
-GUARD_STATE = 8                                  # DVD_GUARD_STATE: doubles of the state block
 GUARD_NORM, GUARD_COEF, GUARD_BAD, GUARD_SKIP, GUARD_SEEN, GUARD_SKIPPED, GUARD_CLIPPED = range(7)
 
 
@@ -565,7 +556,7 @@ def GUARD_CHAIN(n):
 
 
 def grad_guard_ws_bytes(n):
-    return int(L.lib().dvd_grad_guard_ws_bytes(_ll(n)))
+    return int(L.lib().dvd_grad_guard_ws_bytes(int(n)))
 
 
 def grad_guard_ws_views(ws, n):
@@ -581,18 +572,14 @@ def grad_guard(g, max_norm, skip_nonfinite, step, ws, state, ring=None):
     (float64[R][4], optional) receives row (step - 1) % R = step, norm, coef, bad.  Two launches, no host sync."""
     assert g.dtype == torch.float32 and state.dtype == torch.float64 and state.numel() == GUARD_STATE
     assert ring is None or (ring.dtype == torch.float64 and ring.dim() == 2 and ring.shape[1] == 4)
-    L.check(L.lib().dvd_grad_guard(L.ptr(g), _ll(g.numel()), _f(max_norm), int(bool(skip_nonfinite)), _ll(step), L.ptr(ws),
+    L.check(L.lib().dvd_grad_guard(L.ptr(g), g.numel(), float(max_norm), int(bool(skip_nonfinite)), int(step), L.ptr(ws),
                                    L.ptr(state), L.ptr(ring), 0 if ring is None else int(ring.shape[0]), L.stream()))
 
 
 def adam_guard_step(p, g, m, v, ema, lr, b1, b2, eps, step, decay, state):
     """adam_ema_step (ema a tensor) or adam_step (ema None) on g * coef32 of `state`; on a skipped step nothing is written."""
-    L.check(L.lib().dvd_adam_guard_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), _ll(p.numel()), _f(lr), _f(b1),
-                                        _f(b2), _f(eps), int(step), _f(decay), L.ptr(state), L.stream()))
-
-
-ORTHO_COLS = 8                                   # DVD_ORTHO_COLS of include/dvdgan_hip.h: off, h, w | planner columns
-ORTHO_OFF, ORTHO_H, ORTHO_W = 0, 1, 2
+    L.check(L.lib().dvd_adam_guard_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), p.numel(), float(lr), b1, b2, eps,
+                                        int(step), float(decay), L.ptr(state), L.stream()))
 
 
 def ortho_prepare(items):
@@ -602,7 +589,7 @@ def ortho_prepare(items):
         and items.shape[1] == ORTHO_COLS
     lib = L.lib()
     ws = C.c_longlong(0)
-    tiles = lib.dvd_ortho_prepare(C.c_void_p(items.data_ptr()), int(items.shape[0]), C.byref(ws))
+    tiles = lib.dvd_ortho_prepare(items.data_ptr(), int(items.shape[0]), C.byref(ws))
     if tiles < 0:
         L.check(int(tiles))
     return int(tiles), int(ws.value)
@@ -612,21 +599,18 @@ def ortho_grad(p, g, items_host, items_dev, strength, ws, penalty=None):
     """g += 2 * strength * M W for every matrix of the prepared table (views of the flat fp32 buffers p and g at equal offsets),
     M = W W^T with a zero diagonal, in two launches; `penalty` (a float64 device scalar) receives sum 1/2 ||M||_F^2."""
     assert p.dtype == g.dtype == torch.float32 and (penalty is None or penalty.dtype == torch.float64)
-    L.check(L.lib().dvd_ortho_grad(L.ptr(p), L.ptr(g), C.c_void_p(items_host.data_ptr()), L.ptr(items_dev),
-                                   int(items_host.shape[0]), _f(strength), L.ptr(ws), L.ptr(penalty), L.stream()))
+    L.check(L.lib().dvd_ortho_grad(L.ptr(p), L.ptr(g), items_host.data_ptr(), L.ptr(items_dev),
+                                   int(items_host.shape[0]), float(strength), L.ptr(ws), L.ptr(penalty), L.stream()))
 
 
 def ema_step(ema, p, decay):
-    L.check(L.lib().dvd_ema_step(L.ptr(ema), L.ptr(p), _ll(p.numel()), _f(decay), L.stream()))
+    L.check(L.lib().dvd_ema_step(L.ptr(ema), L.ptr(p), p.numel(), float(decay), L.stream()))
 
 
 def swap_(a, b):
     """Exchange the contents of two fp32 tensors of equal size."""
     assert a.numel() == b.numel() and a.dtype == b.dtype == torch.float32
-    L.check(L.lib().dvd_swap_f32(L.ptr(a), L.ptr(b), _ll(a.numel()), L.stream()))
-
-
-METRICS_SIGNED, METRICS_QUANTIZE = 1, 2          # DVD_METRICS_* of include/dvdgan_hip.h
+    L.check(L.lib().dvd_swap_f32(L.ptr(a), L.ptr(b), a.numel(), L.stream()))
 
 
 def frame_metrics(pred, p_strides, target, t_strides, B, T, Cc, H, W, flags, mse, ssim):
@@ -634,11 +618,10 @@ def frame_metrics(pred, p_strides, target, t_strides, B, T, Cc, H, W, flags, mse
     channel) strides in elements are p_strides / t_strides and whose H x W planes are contiguous; fills the fp32 device
     buffers mse / ssim (B * T values each, frame b * T + t)."""
     lib = L.lib()
-    nbytes = lib.dvd_frame_metrics_ws_bytes(_ll(B), T, Cc, H, W)
+    nbytes = lib.dvd_frame_metrics_ws_bytes(int(B), T, Cc, H, W)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device) if nbytes else None
-    L.check(lib.dvd_frame_metrics(C.c_void_p(pred.data_ptr()), *(_ll(s) for s in p_strides),
-                                  C.c_void_p(target.data_ptr()), *(_ll(s) for s in t_strides),
-                                  _ll(B), T, Cc, H, W, int(flags), L.ptr(mse), L.ptr(ssim), L.ptr(ws), L.stream()))
+    L.check(lib.dvd_frame_metrics(pred.data_ptr(), *map(int, p_strides), target.data_ptr(), *map(int, t_strides), int(B), T, Cc,
+                                  H, W, int(flags), L.ptr(mse), L.ptr(ssim), L.ptr(ws), L.stream()))
 
 
 def clip_gather(blob, clips_host, clips_dev, tables, out, ms, norm_value=255.0):
@@ -650,13 +633,9 @@ def clip_gather(blob, clips_host, clips_dev, tables, out, ms, norm_value=255.0):
     assert three == 3 and S == S2 and out.dtype == torch.float32 and blob.dtype == torch.uint8 and tables.dtype == torch.int32
     assert clips_host.dtype == clips_dev.dtype == torch.int64 and not clips_host.is_cuda and clips_host.is_contiguous()
     assert clips_host.numel() == clips_dev.numel() == B * (L.CLIP_COLS + T)
-    L.check(L.lib().dvd_clip_gather(L.ptr(blob), _ll(blob.numel()), C.c_void_p(clips_host.data_ptr()), L.ptr(clips_dev),
-                                    L.ptr(tables), _ll(tables.numel()), L.ptr(out), _ll(B), T, S, _f(norm_value), L.ptr(ms),
-                                    L.stream()))
+    L.check(L.lib().dvd_clip_gather(L.ptr(blob), blob.numel(), clips_host.data_ptr(), L.ptr(clips_dev), L.ptr(tables),
+                                    tables.numel(), L.ptr(out), B, T, S, float(norm_value), L.ptr(ms), L.stream()))
     return out
-
-
-SHEET_FILL, SHEET_SIGNED = 1, 2                  # DVD_SHEET_* of include/dvdgan_hip.h
 
 
 def sample_sheet_shape(total_slots, H, W, nrow, padding, row_prefix=0):
@@ -674,7 +653,7 @@ def sample_sheet(src, strides, n_sheets, n_tiles, H, W, first_slot, total_slots,
     """dvd_sample_sheet: device fp32 `src` (views welcome: only the data pointer is taken) seen as [n_sheets][n_tiles][3][H][W]
     with (sheet, tile, channel) `strides` in elements -> the uint8 device buffer `dst` [n_sheets][Hs][row_prefix + 3 Ws]."""
     assert src.is_cuda and src.dtype == torch.float32 and dst.dtype == torch.uint8 and dst.device == src.device
-    L.check(L.lib().dvd_sample_sheet(C.c_void_p(src.data_ptr()), *(_ll(s) for s in strides), _ll(n_sheets), int(n_tiles), int(H),
-                                     int(W), int(first_slot), int(total_slots), int(nrow), int(padding), _f(pad_value),
+    L.check(L.lib().dvd_sample_sheet(src.data_ptr(), *map(int, strides), int(n_sheets), int(n_tiles), int(H),
+                                     int(W), int(first_slot), int(total_slots), int(nrow), int(padding), float(pad_value),
                                      int(row_prefix), int(flags), L.ptr(dst), L.stream()))
     return dst

@@ -4,8 +4,29 @@ import os
 
 import torch
 
+# ---- every value copied from a `#define DVD_*` of include/dvdgan_hip.h; HEADER_CONSTANTS below names each one
+# (tests/test_abi_cpu.py compares them with the header)
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
+(STRUCT_CONV, STRUCT_WGRAD, STRUCT_GRU, STRUCT_SN_ITEM, STRUCT_GRU_STACK, STRUCT_PACK_ITEM, STRUCT_FRAG_ITEM) = range(7)
+GRU_TICKETS = 8192      # zero-initialised counters of dvd_gru_desc.tickets
+GRU_STACK_MAX = 4       # layers of a dvd_gru_stack_desc
+BN_NREP = 16            # copies of the [2C] sums dvd_bn_stats spreads its atomics over
+SN_SCRATCH = 512        # floats of dvd_sn_backward's scratch
+GUARD_CH = 16384        # elements per workgroup of dvd_grad_guard's norm pass
+GUARD_STATE = 8         # doubles of its state block
+ORTHO_COLS = 8          # dvd_ortho_grad's table: off, h, w | planner columns
+ORTHO_OFF, ORTHO_H, ORTHO_W = 0, 1, 2
+METRICS_SIGNED, METRICS_QUANTIZE = 1, 2
+METRICS_MIN_SIDE, METRICS_MAX_SIDE = 11, 256        # the 11 x 11 SSIM window, the kernel's widest row
+# dvd_clip_gather: columns of a clip row, served sizes
+CLIP_COLS = 11
+(CLIP_OFF, CLIP_H, CLIP_W, CLIP_FRAMES, CLIP_X0, CLIP_Y0, CLIP_CW, CLIP_CH, CLIP_FLIP, CLIP_XTAB, CLIP_YTAB) = range(CLIP_COLS)
+CLIP_MAX_SIDE, CLIP_MAX_OUT = 4096, 256
+SHEET_FILL, SHEET_SIGNED = 1, 2
+HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
+                    if name.isupper() and not name.startswith("_") and isinstance(value, int)}
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVD_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip.so")    # (override: A/B builds)
 _lib = None
@@ -32,6 +53,105 @@ class WgradDesc(C.Structure):
                 ("overwrite", C.c_int)]
 
 
+# Every function include/dvdgan_hip.h declares: return code, then one code per parameter in order (blanks only group them).
+# i int, l long long, f float, d double, p any pointer (data, hipStream_t, descriptor, item array, out-parameter: c_void_p takes
+# None, an int, a ctypes array or byref()); returns also v void, s const char*.  tests/test_abi_cpu.py parses the header's
+# prototypes and compares entry by entry: a new entry point is one line here.
+_CTYPES = {"i": C.c_int, "l": C.c_longlong, "f": C.c_float, "d": C.c_double, "p": C.c_void_p, "v": None, "s": C.c_char_p}
+SIGNATURES = {
+    "dvd_abi_version": "i",
+    "dvd_struct_size": "i i",
+    "dvd_prof_enable": "v i",
+    "dvd_prof_report": "l ipp",
+    "dvd_prof_report_variants": "l iippp",
+    "dvd_strerror": "s i",
+    "dvd_conv_forward": "i pp",
+    "dvd_conv_pool2_ok": "i p",
+    "dvd_conv_fragment_major_bytes": "l iii",
+    "dvd_conv_fragment_major": "i ipp iii p",
+    "dvd_conv_fragment_major_batched": "i ipi p",
+    "dvd_conv_wants_fragment_major": "i p",
+    "dvd_conv_thin_image_bytes": "l i",
+    "dvd_conv_thin_image": "i ppi p",
+    "dvd_conv_thin_out_image_bytes": "l",
+    "dvd_conv_thin_out_image": "i ppi p",
+    "dvd_conv_wgrad": "i pp",
+    "dvd_conv_wgrad_ws_floats": "l p",
+    "dvd_pack_conv_weight": "i ipp iiiiiii pp iiiii p",
+    "dvd_pack_conv_weight_batched": "i ipi p",
+    "dvd_to_channels_last": "i ipp lil iiii p",
+    "dvd_from_channels_last": "i ipp lil iiii p",
+    "dvd_convert": "i ipip l p",
+    "dvd_convgru_layer_forward": "i pp",
+    "dvd_convgru_layer_backward": "i pp",
+    "dvd_convgru_ws_floats": "l iiiiii",
+    "dvd_conv_pick_nsplit": "i il iii",
+    "dvd_convgru_stack_ok": "i pi",
+    "dvd_convgru_stack_ws_floats": "l p",
+    "dvd_convgru_stack_forward": "i pp",
+    "dvd_convgru_stack_backward": "i pp",
+    "dvd_debug_stack_ws": "v pi",
+    "dvd_bn_stats": "i ip l ii p p",
+    "dvd_bn_finalize": "i p l i ff i pppp i p",
+    "dvd_cbn_apply": "i ipp l iii pppp i p",
+    "dvd_cbn_backward": "i ipppp l iii pppp i pp i p p",
+    "dvd_cbn_backward_ws_floats": "l lii",
+    "dvd_cbn_backward_reduce": "i ippp l iii pppp i pp i p p",
+    "dvd_cbn_backward_apply": "i ipppp l iii ppppp l i p",
+    "dvd_pool": "i ipp l iiiiiii f p",
+    "dvd_pool_masked": "i ippp l iiiii f p",
+    "dvd_unpool": "i ipp l iiiii f p",
+    "dvd_colsum": "i ip l ii p p",
+    "dvd_add": "i ippp l p",
+    "dvd_sum_leading": "i ipp i l p",
+    "dvd_act_backward": "i ippp l i p",
+    "dvd_vid_downsample": "i pp iiiiii p",
+    "dvd_vid_downsample_cat": "i pipip iiiii p",
+    "dvd_row_copy": "i ppp ll i p",
+    "dvd_sn_power_iter": "i p ii ppp p",
+    "dvd_sn_backward": "i ppppp ii pp p",
+    "dvd_sn_scale": "i ppp l p",
+    "dvd_sn_batched_prepare": "i pip",
+    "dvd_sn_batched": "i pp i p p",
+    "dvd_linear_forward": "i pppp iii p",
+    "dvd_linear_backward": "i pppp i pp iii p",
+    "dvd_embedding_backward": "i ppp l i p",
+    "dvd_relu_spatial_sum": "i ipp l iii p",
+    "dvd_relu_spatial_sum_backward": "i ippp l iii p",
+    "dvd_proj_head_forward": "i pppppppp l i p",
+    "dvd_proj_head_backward": "i ppppppppppp l i p",
+    "dvd_adv_loss": "i p l ii pp f p",
+    "dvd_adam_step": "i pppp l ffff i p",
+    "dvd_adam_ema_step": "i ppppp l ffff i f p",
+    "dvd_ema_step": "i pp l f p",
+    "dvd_swap_f32": "i pp l p",
+    "dvd_grad_guard_ws_bytes": "l l",
+    "dvd_grad_guard": "i p l f i l ppp i p",
+    "dvd_adam_guard_step": "i ppppp l ffff i f p p",
+    "dvd_frame_metrics_ws_bytes": "l l iiii",
+    "dvd_frame_metrics": "i p lll p lll l iiii i ppp p",
+    "dvd_ortho_prepare": "l pip",
+    "dvd_ortho_grad": "i pp pp i f pp p",
+    "dvd_attention_forward": "i ip iiii p ii pppp l i p",
+    "dvd_attention_backward": "i ip iiii p ii pppppp l i p",
+    "dvd_attention_mfma_ok": "i iiiiiiii",
+    "dvd_attention_mfma_forward": "i pipi pppp l i p",
+    "dvd_attention_mfma_backward": "i pipi pppppp l i p",
+    "dvd_attention_kv_forward": "i ip ii p iii p ii pppp l ii p",
+    "dvd_attention_kv_backward": "i ip ii p iii p ii ppppppp l ii p",
+    "dvd_maxpool3d": "i ipp l iiii p",
+    "dvd_maxpool3d_backward": "i ippp l iiii p",
+    "dvd_sepattn_work_floats": "l iiiiii",
+    "dvd_sepattn_forward": "i ip iiii p ii pppppppp l iiii p",
+    "dvd_sepattn_backward": "i ip iii ppppppppppppp iii p l iiii p",
+    "dvd_clip_to_tensor": "i ppp l iii f p p",
+    "dvd_clip_gather_band_rows": "i ii",
+    "dvd_clip_gather": "i p l ppp l p l ii f p p",
+    "dvd_sample_sheet_shape": "i iiiiii ppp",
+    "dvd_sample_sheet": "i p lll l iiiiiii f ii p p",
+}
+
+
 def lib():
     """The loaded shared library.  Raises (never falls back) when it has not been built."""
     global _lib
@@ -41,20 +161,15 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(dvd_gan_amd has no CPU / eager fallback)")
         _lib = C.CDLL(LIB_PATH)
-        _lib.dvd_strerror.restype = C.c_char_p
-        _lib.dvd_conv_wgrad_ws_floats.restype = C.c_longlong
-        _lib.dvd_sepattn_work_floats.restype = C.c_longlong
-        _lib.dvd_conv_fragment_major_bytes.restype = C.c_longlong
-        _lib.dvd_convgru_ws_floats.restype = C.c_longlong
-        _lib.dvd_conv_thin_image_bytes.restype = C.c_longlong
-        _lib.dvd_conv_thin_out_image_bytes.restype = C.c_longlong
-        _lib.dvd_convgru_stack_ws_floats.restype = C.c_longlong
-        _lib.dvd_cbn_backward_ws_floats.restype = C.c_longlong
-        _lib.dvd_frame_metrics_ws_bytes.restype = C.c_longlong
-        _lib.dvd_ortho_prepare.restype = C.c_longlong
-        _lib.dvd_grad_guard_ws_bytes.restype = C.c_longlong
         if _lib.dvd_abi_version() != ABI_VERSION:
             raise RuntimeError("libdvdgan_hip.so ABI version mismatch: rebuild it")
+        # signature handshake: every entry point gets its declared types, so a plain Python int reaches a `long long` whole
+        for name, sig in SIGNATURES.items():
+            fn = getattr(_lib, name, None)
+            if fn is None:
+                _lib = None
+                raise RuntimeError(f"libdvdgan_hip.so exports no {name} -- lib.py and include/dvdgan_hip.h disagree")
+            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
         # layout handshake: every descriptor mirror below must have the size the library was compiled with
         for which, mirror in STRUCT_MIRRORS.items():
             want = _lib.dvd_struct_size(which)
@@ -66,12 +181,6 @@ def lib():
 
 
 ABI_VERSION = 13
-BN_NREP = 16            # DVD_BN_NREP of include/dvdgan_hip.h
-SN_SCRATCH = 512        # DVD_SN_SCRATCH
-# dvd_clip_gather: columns of a clip row (DVD_CLIP_*), served sizes
-CLIP_COLS = 11
-(CLIP_OFF, CLIP_H, CLIP_W, CLIP_FRAMES, CLIP_X0, CLIP_Y0, CLIP_CW, CLIP_CH, CLIP_FLIP, CLIP_XTAB, CLIP_YTAB) = range(CLIP_COLS)
-CLIP_MAX_SIDE, CLIP_MAX_OUT = 4096, 256
 
 
 def check(code):
@@ -138,12 +247,6 @@ class GruDesc(C.Structure):
                 ("tickets", C.c_void_p), ("combine_max", C.c_int), ("ns_cap", C.c_int)]
 
 
-GRU_TICKETS = 8192                      # == DVD_GRU_TICKETS
-
-
-GRU_STACK_MAX = 4                       # == DVD_GRU_STACK_MAX
-
-
 class GruStackDesc(C.Structure):        # == dvd_gru_stack_desc
     _fields_ = [("n_layers", C.c_int), ("layer_policy", C.c_int), ("run", C.c_int), ("cin", C.c_int * GRU_STACK_MAX),
                 ("layer", GruDesc * GRU_STACK_MAX),
@@ -171,4 +274,5 @@ class FragItem(C.Structure):            # == dvd_frag_item
 
 
 # dvd_struct_size(which) -> ctypes mirror (DVD_STRUCT_* of include/dvdgan_hip.h)
-STRUCT_MIRRORS = {0: ConvDesc, 1: WgradDesc, 2: GruDesc, 3: SnItem, 4: GruStackDesc, 5: PackItem, 6: FragItem}
+STRUCT_MIRRORS = {STRUCT_CONV: ConvDesc, STRUCT_WGRAD: WgradDesc, STRUCT_GRU: GruDesc, STRUCT_SN_ITEM: SnItem,
+                  STRUCT_GRU_STACK: GruStackDesc, STRUCT_PACK_ITEM: PackItem, STRUCT_FRAG_ITEM: FragItem}

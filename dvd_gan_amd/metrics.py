@@ -6,7 +6,7 @@ import torch
 
 from . import kern as K
 
-MIN_SIDE, MAX_SIDE = 11, 256            # DVD_METRICS_MIN_SIDE / _MAX_SIDE: the 11 x 11 window, the kernel's widest row
+from .lib import METRICS_MAX_SIDE as MAX_SIDE, METRICS_MIN_SIDE as MIN_SIDE
 
 
 def _batch_strides(t, name):

@@ -154,8 +154,7 @@ def prefetch_spectral_norm(net, dtype):
         side.wait_stream(main)
         with torch.cuda.stream(side):
             table = host.to(dev, non_blocking=True)
-            L.check(L.lib().dvd_sn_batched(items, C.c_void_p(table.data_ptr()), n, C.c_void_p(scratch.data_ptr()),
-                                           C.c_void_p(side.cuda_stream)))
+            L.check(L.lib().dvd_sn_batched(items, table.data_ptr(), n, scratch.data_ptr(), side.cuda_stream))
             pb.run()
             ev = torch.cuda.Event()
             ev.record(side)

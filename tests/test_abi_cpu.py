@@ -75,6 +75,144 @@ def test_descriptor_layouts_match_the_library():
         L.lib()
 
 
+_PARAM_CODES = {"long long": "l", "int": "i", "float": "f", "double": "d"}
+
+
+def declared_signatures(header=HEADER):
+    """name -> "<return code><parameter codes>" of every prototype of the header, by a fixed rule: any `*` -> p, long long -> l,
+    int -> i, float -> f, double -> d, a lone void -> no parameters; returns also v (void) and s (const char*).  Raises on a
+    parameter type outside the rule; a prototype the pattern misses shows as a name declared_symbols() has and this has not."""
+    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"\b(const\s+char\s*\*|void|int|long\s+long)\s*(dvd_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        ret = "s" if "*" in ret else "v" if ret == "void" else _PARAM_CODES[" ".join(ret.split())]
+        codes = ""
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            if "*" in p:
+                codes += "p"
+                continue
+            words = [w for w in p.split() if w != "const"]
+            kind = " ".join(words[:-1])                  # (the last word is the parameter's name)
+            if kind not in _PARAM_CODES:
+                raise ValueError(f"{name}: parameter {p.strip()!r} has a type the signature codes do not cover")
+            codes += _PARAM_CODES[kind]
+        assert name not in out, name
+        out[name] = ret + codes
+    return out
+
+
+def signature_mismatches(table):
+    want = declared_signatures()
+    assert sorted(want) == declared_symbols() and len(want) == 90       # the pattern missed no prototype
+    assert sorted(table) == sorted(want), sorted(set(table) ^ set(want))
+    return sorted(n for n in want if table[n].replace(" ", "") != want[n])
+
+
+def test_signature_table_matches_the_header():
+    """Signatures, the third part of the handshake (symbols and descriptor sizes above): lib.SIGNATURES, which types every
+    entry point of the loaded library, says what the header's prototypes say."""
+    from dvd_gan_amd import lib as L
+    assert signature_mismatches(L.SIGNATURES) == []
+    # the check can fail: one `long long` declared as `int` is named ...
+    wrong = dict(L.SIGNATURES)
+    assert wrong["dvd_adam_step"].replace(" ", "")[5] == "l"
+    wrong["dvd_adam_step"] = "i pppp i ffff i p"
+    assert signature_mismatches(wrong) == ["dvd_adam_step"]
+    wrong = dict(L.SIGNATURES, dvd_strerror="i i")                        # ... a return type too ...
+    assert signature_mismatches(wrong) == ["dvd_strerror"]
+    del wrong["dvd_swap_f32"]                                             # ... and a missing line
+    with pytest.raises(AssertionError, match="dvd_swap_f32"):
+        signature_mismatches(wrong)
+
+
+def test_unknown_parameter_types_are_refused(tmp_path):
+    path = tmp_path / "h.h"
+    path.write_text("int dvd_abi_version(void);\nint dvd_new_thing(const float* p, size_t n, void* stream);\n")
+    with pytest.raises(ValueError, match="dvd_new_thing.*size_t n"):
+        declared_signatures(str(path))
+
+
+def test_loaded_library_is_fully_typed():
+    import ctypes as C
+    from dvd_gan_amd import lib as L
+    lib = L.lib()
+    kinds = {"i": C.c_int, "l": C.c_longlong, "f": C.c_float, "d": C.c_double, "p": C.c_void_p, "v": None, "s": C.c_char_p}
+    for name, sig in L.SIGNATURES.items():
+        fn, sig = getattr(lib, name), sig.replace(" ", "")
+        assert fn.restype is kinds[sig[0]], name
+        assert list(fn.argtypes) == [kinds[c] for c in sig[1:]], name
+        assert "v" not in sig[1:] and "s" not in sig[1:], name
+    # a table line without a function in the library is refused at load
+    try:
+        L.SIGNATURES["dvd_no_such_entry"] = "i p"
+        L._lib = None
+        with pytest.raises(RuntimeError, match="exports no dvd_no_such_entry"):
+            L.lib()
+    finally:
+        del L.SIGNATURES["dvd_no_such_entry"]
+        L._lib = None
+        L.lib()
+
+
+def test_long_long_arguments_survive_as_plain_ints():
+    """A plain Python int reaches a `long long` parameter whole (untyped, ctypes would pass its low 32 bits as an int)."""
+    import ctypes as C
+    from dvd_gan_amd import lib as L
+    lib = L.lib()
+    for n in (2 ** 31 + 5, 2 ** 33):
+        got = lib.dvd_grad_guard_ws_bytes(n)
+        assert got == lib.dvd_grad_guard_ws_bytes(C.c_longlong(n))
+        assert got >= 12 * -(-n // L.GUARD_CH)                            # the bound of tests/test_guard_cpu.py
+    P_, C_ = 64, 8
+    for frames in (2 ** 31 // P_ + 3, 2 ** 33 + 16):                      # frames * P > 2^31; a frame count above 2^32 whose low word is 16
+        got = lib.dvd_cbn_backward_ws_floats(frames, P_, C_)
+        assert got == lib.dvd_cbn_backward_ws_floats(C.c_longlong(frames), P_, C_)
+        assert got == 0 or got >= frames * 2 * C_                         # refused, or [2C] partial sums for every frame: never for 16 of them
+
+
+def test_float_arguments_convert_by_declaration():
+    import ctypes as C
+    from dvd_gan_amd import lib as L
+    lib = L.lib()
+    p = C.c_void_p(16)                                                    # never dereferenced: refused before any launch
+    for decay in (1.0, 1.5, -0.1, float("nan")):                          # the decay check of tests/test_ema_cpu.py
+        assert lib.dvd_ema_step(p, p, 100, decay, None) == lib.dvd_ema_step(p, p, C.c_longlong(100), C.c_float(decay), None) == -1
+    for max_norm in (0.0, -1.0, float("nan")):                            # the max_norm check of tests/test_guard_cpu.py
+        plain = lib.dvd_grad_guard(p, 100, max_norm, 1, 1, p, p, None, 0, None)
+        assert plain == lib.dvd_grad_guard(p, C.c_longlong(100), C.c_float(max_norm), 1, C.c_longlong(1), p, p, None, 0, None) == -1
+    assert lib.dvd_ema_step(None, p, 100, 0.5, None) == -1                # a good decay gets as far as the pointer check
+
+
+def test_missing_arguments_raise():
+    from dvd_gan_amd import lib as L
+    lib = L.lib()
+    assert lib.dvd_grad_guard_ws_bytes(0) == 0
+    with pytest.raises(TypeError):
+        lib.dvd_grad_guard_ws_bytes()
+    with pytest.raises(TypeError):
+        lib.dvd_ema_step(None, None, 100, 0.5)                            # the stream is missing
+    with pytest.raises(ctypes.ArgumentError):
+        lib.dvd_grad_guard_ws_bytes(1.5)                                  # and a float is no element count
+
+
+def test_header_constants_match_the_header():
+    """Every value lib.py copies from a #define of the header, compared by name."""
+    from dvd_gan_amd import kern as K, lib as L, metrics
+    src = open(HEADER).read()
+    defines = {n: int(v) for n, v in re.findall(r"^#define (DVD_[A-Z0-9_]+)\s+\(?(-?\d+)\)?\s*(?:/\*.*)?$", src, flags=re.M)}
+    assert len(L.HEADER_CONSTANTS) >= 43
+    for name, value in L.HEADER_CONSTANTS.items():
+        assert name in defines, name
+        assert defines[name] == value, (name, value, defines[name])
+    # the groups modules re-export are the checked values, and the descriptor indices are the mirrors' keys
+    for name in ("GUARD_CH", "GUARD_STATE", "ORTHO_COLS", "ORTHO_OFF", "ORTHO_H", "ORTHO_W", "METRICS_SIGNED", "METRICS_QUANTIZE",
+                 "SHEET_FILL", "SHEET_SIGNED"):
+        assert getattr(K, name) is L.HEADER_CONSTANTS["DVD_" + name], name
+    assert (metrics.MIN_SIDE, metrics.MAX_SIDE) == (defines["DVD_METRICS_MIN_SIDE"], defines["DVD_METRICS_MAX_SIDE"])
+    assert set(L.STRUCT_MIRRORS) == {v for n, v in L.HEADER_CONSTANTS.items() if n.startswith("DVD_STRUCT_")}
+    assert {n for n in defines if n.startswith("DVD_STRUCT_")} == {n for n in L.HEADER_CONSTANTS if n.startswith("DVD_STRUCT_")}
+
+
 def test_argument_validation_needs_no_gpu():
     from dvd_gan_amd import lib as L
     lib = L.lib()
@@ -82,8 +220,8 @@ def test_argument_validation_needs_no_gpu():
     assert lib.dvd_conv_forward(ctypes.byref(d), None) == -1
     w = L.WgradDesc()
     assert lib.dvd_conv_wgrad(ctypes.byref(w), None) == -1
-    assert lib.dvd_conv_pick_nsplit(L.BF16, ctypes.c_longlong(1024), 512, 512, 25) == 8       # capped
-    assert lib.dvd_conv_pick_nsplit(L.BF16, ctypes.c_longlong(65536), 512, 256, 25) == 1
+    assert lib.dvd_conv_pick_nsplit(L.BF16, 1024, 512, 512, 25) == 8       # capped
+    assert lib.dvd_conv_pick_nsplit(L.BF16, 65536, 512, 256, 25) == 1
     with pytest.raises(RuntimeError):
         L.check(-2)
 
@@ -301,7 +439,7 @@ def test_attention_refusal_rules_need_no_gpu():
     from dvd_gan_amd import lib as L
     lib = L.lib()
     p = ctypes.c_void_p(1)
-    one = ctypes.c_longlong(1)
+    one = 1
     assert lib.dvd_attention_mfma_ok(L.BF16, 160, 16, 16, 32, 128, 128, 4128) == 0
     assert lib.dvd_attention_mfma_forward(p, 160, p, 128, p, p, p, p, one, 4128, None) == -2
     assert lib.dvd_attention_mfma_backward(p, 160, p, 128, p, p, p, p, p, p, one, 4128, None) == -2

@@ -182,8 +182,8 @@ def kernel_level(a, store, torch):
                                      "clips_per_s": round(1e3 * a.batch / ms, 1)}}), flush=True)
     u8 = torch.randint(0, 256, (a.batch, a.n_frames, a.size, a.size, 3), dtype=torch.uint8, device=out.device)
     fl = torch.zeros(a.batch, dtype=torch.uint8, device=out.device)
-    ms_t = events(lambda: L.check(L.lib().dvd_clip_to_tensor(L.ptr(u8), L.ptr(fl), L.ptr(out), K._ll(a.batch), a.n_frames, a.size,
-                                                             a.size, K._f(255.0), L.ptr(ms6), L.stream())), a.launches, torch)
+    ms_t = events(lambda: L.check(L.lib().dvd_clip_to_tensor(L.ptr(u8), L.ptr(fl), L.ptr(out), a.batch, a.n_frames, a.size,
+                                                             a.size, 255.0, L.ptr(ms6), L.stream())), a.launches, torch)
     print(json.dumps({"kernel_summary": {"crop_sides": sorted({(cw, ch) for _, _, cw, ch in boxes}), "MB_moved": round(nbytes / 1e6, 1),
                                          "ms_min": round(min(best), 4), "ms_max": round(max(best), 4),
                                          "GBps_effective_best": round(nbytes / min(best) / 1e6, 1),
