@@ -14,9 +14,9 @@ __device__ __forceinline__ u32x4 relu16_f32(u32x4 v) {
     v.z = (int32_t)v.z < 0 ? 0u : v.z; v.w = (int32_t)v.w < 0 ? 0u : v.w;
     return v;
 }
-__device__ __forceinline__ uint32_t relu2_bf16(uint32_t v) {
-    uint32_t m = ((v >> 15) & 0x00010001u) * 0xffffu;      // 0xffff in each half whose sign bit is set
-    return v & ~m;
+typedef __attribute__((ext_vector_type(2))) short i16x2;
+__device__ __forceinline__ uint32_t relu2_bf16(uint32_t v) {   // a half whose sign bit is set is a negative int16: one v_pk_max_i16 against 0
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(i16x2, v), i16x2{0, 0}));
 }
 __device__ __forceinline__ u32x4 relu16_bf16(u32x4 v) {
     v.x = relu2_bf16(v.x); v.y = relu2_bf16(v.y); v.z = relu2_bf16(v.z); v.w = relu2_bf16(v.w);
@@ -135,6 +135,78 @@ __device__ __forceinline__ void epi_run(Stage stage, Load load, Compute compute)
     }
 }
 
+// ---------------------------------------------------------------------------- accumulator layouts
+// A wave's sub-tile is 32 rows x 64 columns = 8 quads (16 bytes per lane) in register order.  Two layouts, told apart by the type:
+//   f32x16[2]      v_mfma_f32_32x32x16 (conv_igemm.hip): t[tn], column tn*32 + (lane & 31), row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+//   Acc16<Rows>    v_mfma_f32_16x16x32 (conv_gb.hip): q[h][j], column j*16 + (lane & 15), row Rows::pix(h, 4 (lane >> 4) + r)
+// FragRows: which of the sub-tile's 32 rows (pixels, in the tile's own order) row i of the 16-row A fragment h holds -- bit b of the
+// pixel is bit Bb of (h << 4 | i).  One map per footprint geometry, each brute-forced conflict-free over the four 16-lane groups
+// of ds_read_b128, every tap of 3 x 3 and 5 x 5, with lane l reading 16-byte slot l >> 4 of row l & 15 under the image's swizzle
+// (16 consecutive pixels of one line are 2-way conflicted on every image).
+template <int B0, int B1, int B2, int B3, int B4> struct FragRows {
+    static constexpr int bit(int rid, int b) { return (rid >> b) & 1; }
+    static constexpr int pix(int h, int i) {
+        const int rid = h << 4 | i;
+        return bit(rid, B0) | bit(rid, B1) << 1 | bit(rid, B2) << 2 | bit(rid, B3) << 3 | bit(rid, B4) << 4;
+    }
+};
+using RowsHalo = FragRows<0, 1, 4, 2, 3>;    // 2 lines x 16 px: fragment h = px {0..3, 8..11} + 4 h of both lines (also 4 x 4 frames: lines h, h + 2 of two frames)
+using RowsUp2 = FragRows<0, 2, 3, 4, 1>;     // the same under a nearest x2 upsample: px {0, 1, 4, 5} + {0, 2} + 8 h of both lines
+using RowsF8 = FragRows<0, 1, 2, 4, 3>;      // 4 lines x 8 px of an 8 x 8 frame: lines h and h + 2
+template <class Rows> struct Acc16 { f32x4 q[2][4]; };
+
+__device__ __forceinline__ void acc_zero(f32x16 (&t)[2]) {
+    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    t[0] = z; t[1] = z;
+}
+template <class Rows> __device__ __forceinline__ void acc_zero(Acc16<Rows>& a) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int g = 0; g < 8; ++g) a.q[g >> 2][g & 3] = z;
+}
+// quad g (0 .. 7, a compile-time number after unrolling) of a sub-tile, and v added onto it
+__device__ __forceinline__ u32x4 acc_quad(const f32x16 (&t)[2], int g) {
+    const f32x16& a = t[g >> 2];
+    const int q = g & 3;
+    return u32x4{__float_as_uint(a[4 * q]), __float_as_uint(a[4 * q + 1]), __float_as_uint(a[4 * q + 2]), __float_as_uint(a[4 * q + 3])};
+}
+template <class Rows> __device__ __forceinline__ u32x4 acc_quad(const Acc16<Rows>& a, int g) { return __builtin_bit_cast(u32x4, a.q[g >> 2][g & 3]); }
+__device__ __forceinline__ void acc_add(f32x16 (&t)[2], int g, u32x4 v) {
+    f32x16& a = t[g >> 2];
+    const int q = g & 3;
+    a[4 * q] += __uint_as_float(v.x); a[4 * q + 1] += __uint_as_float(v.y);
+    a[4 * q + 2] += __uint_as_float(v.z); a[4 * q + 3] += __uint_as_float(v.w);
+}
+template <class Rows> __device__ __forceinline__ void acc_add(Acc16<Rows>& a, int g, u32x4 v) {
+    f32x4& x = a.q[g >> 2][g & 3];
+    x[0] += __uint_as_float(v.x); x[1] += __uint_as_float(v.y); x[2] += __uint_as_float(v.z); x[3] += __uint_as_float(v.w);
+}
+// the sub-tile as a [32 rows][64 columns] fp32 image in the wave's LDS block
+__device__ __forceinline__ void acc_stage(const f32x16 (&t)[2], float* ep, int lane) {
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            ep[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 64 + tn * 32 + (lane & 31)] = t[tn][r];
+}
+// (the 16-lane groups kg = lane >> 4 of one ds_write_b32 group, kg and kg ^ 1, would meet on the same 16 banks four rows apart:
+// the odd groups take column block j ^ 1 in the same instruction)
+template <class Rows> __device__ __forceinline__ void acc_stage(const Acc16<Rows>& a, float* ep, int lane) {
+    const int kg = lane >> 4;
+    const bool odd = kg & 1;
+    float* const e0 = ep + Rows::pix(0, 4 * kg) * 64 + (lane & 15) + (odd ? 16 : 0);
+    float* const e1 = ep + Rows::pix(0, 4 * kg) * 64 + (lane & 15) + (odd ? 0 : 16);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)                   // pix is bitwise: pix(h, 4 kg + r) = pix(0, 4 kg) | pix(h, r)
+                ((j & 1) ? e1 : e0)[Rows::pix(h, r) * 64 + (j >> 1) * 32] = odd ? a.q[h][j ^ 1][r] : a.q[h][j][r];
+            __builtin_amdgcn_sched_barrier(0);            // four selected values at a time: the epilogues have no registers to spare
+        }
+}
+
 // ---------------------------------------------------------------------------- in-launch split-K combine (round 4)
 // A split-K recurrent convolution used to leave ns fp32 slabs [z][M][Cout] for a gate kernel that summed them and applied the
 // ConvGRU gate math: two launches per convolution on a chain of dependent launches.  Here the LAST workgroup of a tile to finish
@@ -147,9 +219,9 @@ __device__ __forceinline__ void epi_run(Stage stage, Load load, Compute compute)
 //                           order, reset the ticket for the next launch on the stream, go on into the gate epilogue.
 // The sum is the same whichever workgroup arrives last: ns == 2 adds the other slab onto the registers (a + b == b + a), ns > 2
 // re-reads all ns slabs, its own included, into zeroed accumulators in slice order.  Slab layout (private to this function):
-// [tile][slice][wave][tm][tn][quad][lane] x 16 bytes.  cdna_hip_programming.md section 5 (split-K reduction recipe).
-template <int TM>
-__device__ __forceinline__ bool splitk_combine(const ConvK& p, f32x16 (&acc)[TM][2], float* lds0, int lane, int z, int ltile) {
+// [tile][slice][wave][tm][quad 0 .. 7, register order of either accumulator layout][lane] x 16 bytes.  cdna_hip_programming.md section 5 (split-K reduction recipe).
+template <int TM, class Acc>
+__device__ __forceinline__ bool splitk_combine(const ConvK& p, Acc (&acc)[TM], float* lds0, int lane, int z, int ltile) {
     constexpr unsigned kWaveBytes = TM * 2 * 4 * 1024;
     constexpr int kSc1 = 16;                          // cache-policy bit 4 on gfx950: sc1
     const int ns = p.nsplit;
@@ -162,13 +234,8 @@ __device__ __forceinline__ bool splitk_combine(const ConvK& p, f32x16 (&acc)[TM]
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const u32x4 v = {__float_as_uint(acc[tm][tn][4 * q]), __float_as_uint(acc[tm][tn][4 * q + 1]),
-                                 __float_as_uint(acc[tm][tn][4 * q + 2]), __float_as_uint(acc[tm][tn][4 * q + 3])};
-                __builtin_amdgcn_raw_buffer_store_b128(v, rs, z * tileBytes + lo + ((tm * 2 + tn) * 4 + q) * 1024, 0, kSc1);
-            }
+        for (int g = 0; g < 8; ++g)
+            __builtin_amdgcn_raw_buffer_store_b128(acc_quad(acc[tm], g), rs, z * tileBytes + lo + (tm * 8 + g) * 1024, 0, kSc1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0)
@@ -182,13 +249,10 @@ __device__ __forceinline__ bool splitk_combine(const ConvK& p, f32x16 (&acc)[TM]
     int s_begin = 0, s_end = ns;
     if (ns == 2) { s_begin = z ^ 1; s_end = s_begin + 1; }
     else {
-        const f32x16 zacc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = zacc;
+        for (int tm = 0; tm < TM; ++tm) acc_zero(acc[tm]);
     }
-    // groups of 4 loads (one 32 x 32 accumulator block), the next group requested before this one is added: 8 loads per lane in
+    // groups of 4 loads (half a sub-tile), the next group requested before this one is added: 8 loads per lane in
     // flight on 32 registers (the scheduling fences keep hipcc from hoisting every load of the unrolled body to the top -- 348
     // registers in the 256 x 128 kernels).  The group behind the last slab gets an out-of-range offset: zeros, no branch.
     u32x4 buf[2][4];
@@ -205,12 +269,7 @@ __device__ __forceinline__ bool splitk_combine(const ConvK& p, f32x16 (&acc)[TM]
             else issue(s + 1, 0, buf[(g + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const u32x4 v = buf[g & 1][i];
-                f32x16& a = acc[g >> 1][g & 1];
-                a[4 * i] += __uint_as_float(v.x); a[4 * i + 1] += __uint_as_float(v.y);
-                a[4 * i + 2] += __uint_as_float(v.z); a[4 * i + 3] += __uint_as_float(v.w);
-            }
+            for (int i = 0; i < 4; ++i) acc_add(acc[g >> 1], (g & 1) * 4 + i, buf[g & 1][i]);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -220,10 +279,10 @@ __device__ __forceinline__ bool splitk_combine(const ConvK& p, f32x16 (&acc)[TM]
 // `ep`: the wave's LDS staging block (32 x 64 floats); col: first of this lane's 8 output columns; row0: first row every
 // row of this workgroup's tile is relative to (the buffer descriptors start there, offsets stay 32-bit); relrow(tm, j): this
 // lane's row of round j of sub-tile tm, relative to row0, or a negative number when it lies past M.
-// DEEP: deeper operand pipelines for the gate epilogues (kernels whose accumulators live in the unified register file can spend the
+// `acc`: either accumulator layout (above).  DEEP: deeper operand pipelines for the gate epilogues (kernels whose accumulators live in the unified register file can spend the
 // registers of already-staged sub-tiles on operands in flight)
-template <typename T, int TM, int DEEP = 0, bool COMBINE = true, class RelRow>
-__device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][2], float* ep, int lane, int col, int z, int ltile,
+template <typename T, int TM, int DEEP = 0, bool COMBINE = true, class Acc, class RelRow>
+__device__ __forceinline__ void conv_epilogue(const ConvK& p, Acc (&acc)[TM], float* ep, int lane, int col, int z, int ltile,
                                               long long row0, RelRow relrow) {
     constexpr unsigned esz = sizeof(T);
     constexpr int R = 4 * TM;
@@ -232,11 +291,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][
     const bool colv = col < p.Cout;
     const long long rows = (long long)p.M - row0;
     auto stage = [&](int tm) __attribute__((always_inline)) {
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                ep[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 64 + tn * 32 + (lane & 31)] = acc[tm][tn][r];
+        acc_stage(acc[tm], ep, lane);
         __builtin_amdgcn_s_waitcnt(0xc07f);                       // lgkmcnt(0): this wave's LDS writes landed
         __builtin_amdgcn_wave_barrier();
     };

@@ -4,11 +4,14 @@
 //
 // Same GEMM as conv_halo_kernel (conv_igemm.hip): the input footprint of an output patch sits in LDS for all taps of a 32-channel
 // chunk (LDS-DMA, zero fill by out-of-range offsets, double-buffered over chunks).  The weights exist a second time in
-// fragment-major order (dvd_conv_fragment_major): record (tap, chunk, 32-column block nb, k-half pair kk) is the 1 KiB a wave needs
-// for one MFMA B fragment -- lane l = (kh2 = l >> 5, col = l & 31) owns the 8 channels chunk*32 + (2 kk + kh2)*8 .. +7 of output
-// column nb*32 + col at byte l*16 -- so a fragment is ONE coalesced buffer_load_dwordx4 per lane, four per wave and K step,
-// prefetched one K step ahead.  Nothing is handed between waves inside a chunk: no per-tap LDS-DMA, wait or barrier; the waves of a
-// workgroup meet once per chunk (footprint hand-over).
+// fragment-major order (dvd_conv_fragment_major): record (tap, chunk, 32-column block nb, k-half pair kk) is 1 KiB whose 16 bytes
+// l = (kh2 = l >> 5, col = l & 31) are the 8 channels chunk*32 + (2 kk + kh2)*8 .. +7 of output column nb*32 + col.  The tiles
+// multiply on v_mfma_f32_16x16x32_bf16 (the chip holds a higher clock on it than on 32x32x16: profiles/mfma16_numbers.md): one
+// instruction takes a whole 32-channel chunk of 16 pixels x 16 columns; lane l holds k group kg = l >> 4 (channels 8 kg .. 8 kg + 7)
+// of pixel row / column l & 15, so a B fragment is four 256-byte runs of two records -- one buffer_load_dwordx4 per lane, four per
+// wave and K step, prefetched one K step ahead -- and an A fragment one ds_read_b128 of 16 footprint rows (FragRows, conv_common.h).
+// Nothing is handed between waves inside a chunk: no per-tap LDS-DMA, wait or barrier; the waves of a workgroup meet once per chunk
+// (footprint hand-over).
 //
 // Round 5: the filter size KS (3 or 5) is a template parameter.  The tap loop of a chunk is `for (row) { unrolled KS taps }`:
 // the LDS offset of tap ix is an immediate, the weight record advances by a running scalar add (records are [tap][chunk], so the
@@ -30,6 +33,8 @@ namespace {
 constexpr unsigned kRowOOB = 0x80000000u, kStepOOB = 0x40000000u, kRangeCap = 0x3fffffffu;
 
 template <int TM, int WN, int WMV, bool UP2> struct HaloGbCfg {
+    using Rows = std::conditional_t<UP2, RowsUp2, RowsHalo>;      // fragment h = 1: 4 footprint rows to the right of fragment 0
+    static_assert(Rows::pix(1, 0) == (UP2 ? 8 : 4), "fragment 1 = fragment 0 moved 4 footprint columns");
     static constexpr int PITCH = HaloGeo<UP2>::PITCH;
     static constexpr int NWAVE = WMV * WN;
     static constexpr int PH = WMV * TM * 2;                             // patch: PH lines x 16 columns
@@ -39,17 +44,18 @@ template <int TM, int WN, int WMV, bool UP2> struct HaloGbCfg {
     static constexpr int LDSB = 2 * HBYTES + 1024 > EPI ? 2 * HBYTES + 1024 : EPI;
 };
 
-// One K step: 2 * TM units of two MFMAs; the A fragment of unit u + 2 is requested before the MFMAs of unit u, the B fragments of
-// the NEXT step (record nrec) right behind the first MFMA pair -- behind the point where the compiler waits for this step's own
-// fragments -- and, when `foot` is given, the next chunk's footprint DMAs with them.  (The request is unconditional: behind a branch
-// hipcc assumes the smaller outstanding count and drains the prefetch in the middle of a step.)
-template <int TM, bool RELU, class LdA, class Next>
-__device__ __forceinline__ void gb_step(f32x16 (&acc)[TM][2], const bf16x8 (&b)[2][2], LdA ldA, Next next) {
+// One K step = one tap of one 32-channel chunk on v_mfma_f32_16x16x32_bf16: 2 * TM units (sub-tile tm = u >> 1, fragment h = u & 1)
+// of four MFMAs, one per 16-column block of the wave's 64 columns; the A fragment of unit u + 2 is requested before the MFMAs of
+// unit u, the B fragments of the NEXT step (record nrec) right behind the first MFMA group -- behind the point where the compiler
+// waits for this step's own fragments -- and, when `foot` is given, the next chunk's footprint DMAs with them.  (The request is
+// unconditional: behind a branch hipcc assumes the smaller outstanding count and drains the prefetch in the middle of a step.)
+template <int TM, bool RELU, class Rows, class LdA, class Next>
+__device__ __forceinline__ void gb_step(Acc16<Rows> (&acc)[TM], const bf16x8 (&b)[4], LdA ldA, Next next) {
     constexpr int NU = 2 * TM;
 #ifndef DVD_GB_ADEPTH
 #define DVD_GB_ADEPTH 2
 #endif
-    constexpr int AD = DVD_GB_ADEPTH;                 // A fragments requested this many units ahead
+    constexpr int AD = (RELU && TM == 4) ? 1 : DVD_GB_ADEPTH;     // A fragments requested this many units ahead (ReLU on 256 rows: no registers for two)
     bf16x8 a[NU];
 #pragma unroll
     for (int u = 0; u < AD && u < NU; ++u) a[u] = ldA(u);
@@ -57,11 +63,11 @@ __device__ __forceinline__ void gb_step(f32x16 (&acc)[TM][2], const bf16x8 (&b)[
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
         if (u + AD < NU) a[u + AD] = ldA(u + AD);
-        const int kk = u / TM, tm = u % TM;
+        const int tm = u >> 1, h = u & 1;
         if constexpr (RELU) a[u] = __builtin_bit_cast(bf16x8, relu16_bf16(__builtin_bit_cast(u32x4, a[u])));
 #pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u], b[kk][tn], acc[tm][tn], 0, 0, 0);
+        for (int j = 0; j < 4; ++j)
+            acc[tm].q[h][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b[j], acc[tm].q[h][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (u == 0) {
 #ifndef DVD_EXP_NODMA
@@ -80,6 +86,7 @@ __device__ __forceinline__ void conv_halo_gb_tile(const ConvK& p, char* const sm
     using T = bf16_t;
     using G = HaloGeo<UP2>;
     using Cfg = HaloGbCfg<TM, WN, WMV, UP2>;
+    using Rows = typename Cfg::Rows;
     constexpr int NWAVE = Cfg::NWAVE;
     constexpr int PITCH = G::PITCH;
     constexpr int BNt = WN * 64;
@@ -92,11 +99,12 @@ __device__ __forceinline__ void conv_halo_gb_tile(const ConvK& p, char* const sm
     char* const hbuf0 = &smem[0];
     char* const dump = &smem[2 * HBYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
+    const int wm = wave / WN, wn = wave % WN, kg = lane >> 4;
     const int n0 = nt * BNt;
     const int pw = p.W >> 4, ppf = pw * (p.H / PH);
-    const int ft = mt / ppf, pidx = mt - ft * ppf;
-    const int y0 = (pidx / pw) * PH, x0 = (pidx % pw) * 16;
+    // (uniform, but the divisions run on the vector unit: back into scalar registers, or they occupy vector registers to the epilogue)
+    const int ft = __builtin_amdgcn_readfirstlane(mt / ppf), pidx = mt - ft * ppf;
+    const int y0 = __builtin_amdgcn_readfirstlane((pidx / pw) * PH), x0 = __builtin_amdgcn_readfirstlane((pidx % pw) * 16);
     const int nouter = p.kchunks * p.kt;
     const int per = (nouter + p.nsplit - 1) / p.nsplit;
     const int oc_begin = z * per, oc_end = min(nouter, oc_begin + per);
@@ -118,68 +126,70 @@ __device__ __forceinline__ void conv_halo_gb_tile(const ConvK& p, char* const sm
     const __amdgpu_buffer_rsrc_t rwq = __builtin_amdgcn_make_buffer_rsrc(
         (void*)p.wq, 0, (unsigned)((size_t)p.kt * ntap2 * p.kchunks * nb32 * 2048), 0x00020000);
     // footprint row of DMA group i for this lane: its logical 16-byte slot is XOR-swizzled into the offset (see HaloGeo)
-    auto hrow = [&](int i, int& hy, int& hx) __attribute__((always_inline)) {
+    auto hrow = [&](int i, int lrow, int& hy, int& hx) __attribute__((always_inline)) {
         const int h = (i * NWAVE + wu) * 16 + lrow;
         hy = h / PITCH; hx = h - hy * PITCH;
     };
-    unsigned hoff[NH];
-#pragma unroll
-    for (int i = 0; i < NH; ++i) {
+    auto hoff_of = [&](int i, int ln) __attribute__((always_inline)) -> unsigned {
         const int g = i * NWAVE + wu;
         int hy, hx;
-        hrow(i, hy, hx);
+        hrow(i, ln >> 2, hy, hx);
         const int yin = iy_lo + hy, xin = ix_lo + hx;
-        const int hq = (lane & 3) ^ G::sw(hy, hx);
+        const int hq = (ln & 3) ^ G::sw(hy, hx);
         const bool ok = g < HG && hy < HHa && hx < HWa && (unsigned)yin < (unsigned)p.Hin && (unsigned)xin < (unsigned)p.Win;
-        hoff[i] = ok ? (unsigned)(yin * p.Win + xin) * ldb + hq * 16 : kRowOOB;
-    }
+        return ok ? (unsigned)(yin * p.Win + xin) * ldb + hq * 16 : kRowOOB;
+    };
+    // The 256-row tile with ReLU on its fragments has no registers left for the NH offsets across the K loop (they went to scratch):
+    // it forms them again for every footprint, once per chunk, from an opaque copy of the lane index.
+    constexpr bool REOFF = RELU && TM == 4;
+    unsigned hoff[NH];
+#pragma unroll
+    for (int i = 0; i < NH; ++i) hoff[i] = REOFF ? 0u : hoff_of(i, lane);
     const bool ragged = (p.C & 31) != 0;                                 // last chunk holds fewer than 32 channels (uniform)
     auto dmaH = [&](int hb, int cc_, int it_) __attribute__((always_inline)) {
         const int dt_ = it_ - (p.kt >> 1);
         const bool ok_ = (unsigned)(tt + dt_) < (unsigned)p.T || p.kt == 1;
         const unsigned ud_ = ok_ ? (unsigned)(ft + dt_ - base_frame) * (unsigned)fbytes + cc_ * 64 : kStepOOB;
         const bool part_ = ragged && cc_ == p.kchunks - 1;
+        int ln_ = lane;
+        if (part_ || REOFF) asm volatile("" : "+v"(ln_));                // (opaque: hoisted out of the K loop the slots below cost NH registers)
 #pragma unroll
         for (int i = 0; i < NH; ++i) {
             const int g = i * NWAVE + wu;
             char* dst_ = g < HG ? hbuf0 + hb * HBYTES + g * 1024 : dump;
-            unsigned off_ = hoff[i] + ud_;
+            unsigned off_ = (REOFF ? hoff_of(i, ln_) : hoff[i]) + ud_;
             if (part_) {                                                 // channels past C: zeros (rare: thin / odd-width inputs)
                 int hy, hx;
-                hrow(i, hy, hx);
-                const int hq = (lane & 3) ^ G::sw(hy, hx);
+                hrow(i, ln_ >> 2, hy, hx);
+                const int hq = (ln_ & 3) ^ G::sw(hy, hx);
                 off_ = cc_ * 32 + hq * 8 < p.C ? off_ : kRowOOB;
             }
             dma16(rin, dst_, off_);
         }
     };
-    // B fragments: voffset = this wave's column half + lane slot (per lane), soffset = record of (tap, chunk, N tile) (uniform)
-    const unsigned bvoff = (unsigned)(wn * 2 * 2048 + lane * 16);
+    // B fragments: the 16 columns x 32 channels of column block j (0 .. 3) of this wave's 64 columns sit in the record's block
+    // nb = j >> 1, k-half pair kg >> 1, at its lanes (kg & 1) * 32 + (j & 1) * 16 + column.  voffset = this wave's column half + that
+    // slot without j (per lane), soffset = record of (tap, chunk, N tile) (uniform) + j's part
+    const unsigned bvoff = (unsigned)(wn * 2 * 2048 + (kg >> 1) * 1024 + ((kg & 1) * 32 + (lane & 15)) * 16);
     const unsigned bnt = (unsigned)(nt * (BNt / 32)) * 2048u;
     const unsigned brec = (unsigned)nb32 * 2048u;                       // bytes per (tap, chunk)
     const unsigned tapstep = (unsigned)p.kchunks * brec;                // record stride between two taps of one chunk
-    auto ldBq = [&](bf16x8 (&b)[2][2], unsigned rec) __attribute__((always_inline)) {
+    auto ldBq = [&](bf16x8 (&b)[4], unsigned rec) __attribute__((always_inline)) {
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-                b[kk][tn] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rwq, bvoff, rec + (unsigned)(tn * 2048 + kk * 1024), 0));
+        for (int j = 0; j < 4; ++j)
+            b[j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rwq, bvoff, rec + (unsigned)((j >> 1) * 2048 + (j & 1) * 256), 0));
     };
     // record of tap 0 of outer index (chunk cc, time tap it)
     auto rec0 = [&](int cc_, int it_) __attribute__((always_inline)) -> unsigned {
         return ((unsigned)(it_ * ntap2) * p.kchunks + cc_) * brec + bnt;
     };
 
-    f32x16 acc[TM][2];
-    {
-        const f32x16 zacc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    Acc16<Rows> acc[TM];
 #pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) acc[a][b] = zacc;
-    }
-    const int l31 = lane & 31, kh2 = lane >> 5;
-    const int px = l31 & 15, py0 = wm * (TM * 2) + (l31 >> 4);
+    for (int a = 0; a < TM; ++a) acc_zero(acc[a]);
+    // this lane's A row: pixel Rows::pix(h, lane & 15) of each sub-tile (two lines x 16 px) and its channels 8 kg .. 8 kg + 7
+    const int pix0 = Rows::pix(0, lane & 15);
+    const int px = pix0 & 15, py0 = wm * (TM * 2) + (pix0 >> 4);
     constexpr int TMSTRIDE = (UP2 ? 1 : 2) * PITCH * 64;
 #ifdef DVD_EXP_NOMAIN
     const int nouter_z = 0;
@@ -189,7 +199,7 @@ __device__ __forceinline__ void conv_halo_gb_tile(const ConvK& p, char* const sm
     if (nouter_z > 0) {
         int m_cc = oc_begin / p.kt, m_it = oc_begin - m_cc * p.kt;      // (chunk, dt) being multiplied
         int h_cc = m_cc, h_it = m_it;                                   // ... of the next footprint to fetch
-        bf16x8 bq0[2][2], bq1[2][2];
+        bf16x8 bq0[4], bq1[4];
         unsigned rec = rec0(m_cc, m_it);
         dmaH(0, h_cc, h_it);
         if (++h_it == p.kt) { h_it = 0; ++h_cc; }
@@ -201,19 +211,19 @@ __device__ __forceinline__ void conv_halo_gb_tile(const ConvK& p, char* const sm
         // the accumulators at the join (408 spilled registers in the 256 x 128 tile).  Chunk boundaries (footprint hand-over, next
         // chunk's record) are uniform side blocks of the row that ends / starts a chunk.
         int hb = 0, iy = 0, left = nouter_z;                            // footprint buffer, filter row, chunks left incl. the current
-        auto row = [&](bf16x8 (&b0)[2][2], bf16x8 (&b1)[2][2]) __attribute__((always_inline)) {
+        auto row = [&](bf16x8 (&b0)[4], bf16x8 (&b1)[4]) __attribute__((always_inline)) {
             const bool first = iy == 0, last = iy == KS - 1, more = left > 1;
             const int hy = UP2 ? ((py0 + iy - pad) >> 1) + cpad : py0 + iy;
             const char* const Arow = hbuf0 + hb * HBYTES + hy * (PITCH * 64);
 #pragma unroll
             for (int ix = 0; ix < KS; ++ix) {
                 const int hx = UP2 ? ((px + ix - pad) >> 1) + cpad : px + ix;
-                const int swz = G::sw(hy, hx);
+                const int swz[2] = {G::sw(hy, hx), G::sw(hy, hx + 4)};
                 const char* const Ah = Arow + hx * 64;
                 auto ldA = [&](int u) __attribute__((always_inline)) -> bf16x8 {
-                    const int kk = u / TM, tm = u % TM, slot = kk * 2 + kh2;
-                    const int sl = (UP2 && (tm & 1)) ? (slot ^ 2) : slot;
-                    return *reinterpret_cast<const bf16x8*>(Ah + tm * TMSTRIDE + ((sl ^ swz) << 4));
+                    const int tm = u >> 1, h = u & 1;
+                    const int sl = (UP2 && (tm & 1)) ? (kg ^ 2) : kg;        // one footprint line down: sw + 2
+                    return *reinterpret_cast<const bf16x8*>(Ah + tm * TMSTRIDE + h * 256 + ((sl ^ swz[h]) << 4));
                 };
                 unsigned nrec = rec + tapstep;
                 if (ix == KS - 1 && last) {                             // next chunk's first record; none left: re-read this one
@@ -252,11 +262,15 @@ __device__ __forceinline__ void conv_halo_gb_tile(const ConvK& p, char* const sm
     }
     __syncthreads();
 
-    float* ep = reinterpret_cast<float*>(&smem[0]) + wave * (32 * 64);
-    const int ecol = (lane & 7) * 8, erow = lane >> 3;
+    // (the epilogue's lane values come from an opaque copy of the thread index: carried across the K loop they cost it registers)
+    int te = tid;
+    asm volatile("" : "+v"(te));
+    const int elane = te & 63, ewave = te >> 6, ewm = ewave / WN, ewn = ewave % WN;
+    float* ep = reinterpret_cast<float*>(&smem[0]) + ewave * (32 * 64);
+    const int ecol = (elane & 7) * 8, erow = elane >> 3;
     const long long frame_row0 = (long long)ft * (p.H * p.W);
-    conv_epilogue<T, TM, DVD_GB_EPI_DEEP>(p, acc, ep, lane, n0 + wn * 64 + ecol, z, ltile, frame_row0, [&](int tm, int j) __attribute__((always_inline)) {
-        const int pi = wm * (TM * 32) + tm * 32 + j * 8 + erow;
+    conv_epilogue<T, TM, DVD_GB_EPI_DEEP>(p, acc, ep, elane, n0 + ewn * 64 + ecol, z, ltile, frame_row0, [&](int tm, int j) __attribute__((always_inline)) {
+        const int pi = ewm * (TM * 32) + tm * 32 + j * 8 + erow;
         return (y0 + (pi >> 4)) * p.W + x0 + (pi & 15);
     });
 }
@@ -276,8 +290,9 @@ __device__ __forceinline__ TileMN tile_of(int nmajor, int tilesN, int t, int nti
     return o;
 }
 
+// (waves per SIMD the register allocation must leave room for: three of the 128-row tiles, two of the 256-row tiles)
 template <int TM, int WN, int WMV, bool RELU, bool UP2, int KS>
-__global__ __launch_bounds__(256, 2) void conv_halo_gb_kernel(ConvK p) {
+__global__ __launch_bounds__(256, TM == 2 ? 3 : 2) void conv_halo_gb_kernel(ConvK p) {
     __shared__ __attribute__((aligned(16))) char smem[HaloGbCfg<TM, WN, WMV, UP2>::LDSB];
     const int bid = xcd_order(blockIdx.x, gridDim.x);
     const TileMN t = tile_of(p.nmajor, p.tilesN, bid, gridDim.x);
@@ -291,6 +306,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo_gb_kernel(ConvK p) {
 // 16-byte slot swizzle: (line of the footprint) & 3 -- brute-forced conflict-free for both ds_read_b128 lane groups, every tap,
 // S = 8 (a 32-row sub-tile = 4 lines of one frame) and S = 4 (= 2 frames).
 template <int TM, int S> struct HaloGbsCfg {
+    using Rows = std::conditional_t<S == 8, RowsF8, RowsHalo>;           // fragment h = 1: one footprint line below fragment 0
+    static_assert(Rows::pix(1, 0) == S, "fragment 1 = fragment 0 moved one line down");
     static constexpr int PITCH = S + 4, FR = PITCH * PITCH;             // rows per frame footprint
     static constexpr int G = TM * 64 / (S * S);                         // frames per tile
     static constexpr int HG = (G * FR + 15) / 16;
@@ -303,6 +320,7 @@ template <int TM, int S, bool RELU, int KS>
 __device__ __forceinline__ void conv_halo_gbs_tile(const ConvK& p, char* const smem, const int mt, const int nt, const int z, const int ltile) {
     using T = bf16_t;
     using Cfg = HaloGbsCfg<TM, S>;
+    using Rows = typename Cfg::Rows;
     constexpr int WN = 2, NWAVE = 4, BNt = 128;
     constexpr int PITCH = Cfg::PITCH, FR = Cfg::FR, G = Cfg::G, HG = Cfg::HG, HBYTES = Cfg::HBYTES;
     constexpr int NH = (HG + NWAVE - 1) / NWAVE;
@@ -311,7 +329,7 @@ __device__ __forceinline__ void conv_halo_gbs_tile(const ConvK& p, char* const s
     char* const hbuf0 = &smem[0];
     char* const dump = &smem[2 * HBYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
+    const int wm = wave / WN, wn = wave % WN, kg = lane >> 4;
     const int n0 = nt * BNt;
     const int ft0 = mt * G, nframes = p.M / SS;
     const int per = (p.kchunks + p.nsplit - 1) / p.nsplit;
@@ -328,7 +346,7 @@ __device__ __forceinline__ void conv_halo_gbs_tile(const ConvK& p, char* const s
     const int nb32 = p.nb32;
     const __amdgpu_buffer_rsrc_t rwq = __builtin_amdgcn_make_buffer_rsrc(
         (void*)p.wq, 0, (unsigned)((size_t)ntap2 * p.kchunks * nb32 * 2048), 0x00020000);
-    auto hrow = [&](int i, int& fl, int& hy, int& hx) __attribute__((always_inline)) {
+    auto hrow = [&](int i, int lrow, int& fl, int& hy, int& hx) __attribute__((always_inline)) {
         const int h = (i * NWAVE + wu) * 16 + lrow;
         fl = h / FR;
         const int r = h - fl * FR;
@@ -339,7 +357,7 @@ __device__ __forceinline__ void conv_halo_gbs_tile(const ConvK& p, char* const s
     for (int i = 0; i < NH; ++i) {
         const int g = i * NWAVE + wu;
         int fl, hy, hx;
-        hrow(i, fl, hy, hx);
+        hrow(i, lrow, fl, hy, hx);
         const int yin = hy - pad, xin = hx - pad;
         const int hq = (lane & 3) ^ (hy & 3);
         const bool ok = g < HG && fl < G && ft0 + fl < nframes && hy < ext && hx < ext && (unsigned)yin < (unsigned)S && (unsigned)xin < (unsigned)S;
@@ -348,6 +366,8 @@ __device__ __forceinline__ void conv_halo_gbs_tile(const ConvK& p, char* const s
     const bool ragged = (p.C & 31) != 0;
     auto dmaH = [&](int hb, int cc_) __attribute__((always_inline)) {
         const bool part_ = ragged && cc_ == p.kchunks - 1;
+        int ln_ = lane;
+        if (part_) asm volatile("" : "+v"(ln_));                         // (opaque: see conv_halo_gb_tile)
 #pragma unroll
         for (int i = 0; i < NH; ++i) {
             const int g = i * NWAVE + wu;
@@ -355,37 +375,30 @@ __device__ __forceinline__ void conv_halo_gbs_tile(const ConvK& p, char* const s
             unsigned off_ = hoff[i] + cc_ * 64;
             if (part_) {
                 int fl, hy, hx;
-                hrow(i, fl, hy, hx);
-                const int hq = (lane & 3) ^ (hy & 3);
+                hrow(i, ln_ >> 2, fl, hy, hx);
+                const int hq = (ln_ & 3) ^ (hy & 3);
                 off_ = cc_ * 32 + hq * 8 < p.C ? off_ : kRowOOB;
             }
             dma16(rin, dst_, off_);
         }
     };
-    const unsigned bvoff = (unsigned)(wn * 2 * 2048 + lane * 16);
+    const unsigned bvoff = (unsigned)(wn * 2 * 2048 + (kg >> 1) * 1024 + ((kg & 1) * 32 + (lane & 15)) * 16);
     const unsigned bnt = (unsigned)(nt * (BNt / 32)) * 2048u;
     const unsigned brec = (unsigned)nb32 * 2048u;
     const unsigned tapstep = (unsigned)p.kchunks * brec;
-    auto ldBq = [&](bf16x8 (&b)[2][2], unsigned rec) __attribute__((always_inline)) {
+    auto ldBq = [&](bf16x8 (&b)[4], unsigned rec) __attribute__((always_inline)) {
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-                b[kk][tn] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rwq, bvoff, rec + (unsigned)(tn * 2048 + kk * 1024), 0));
+        for (int j = 0; j < 4; ++j)
+            b[j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rwq, bvoff, rec + (unsigned)((j >> 1) * 2048 + (j & 1) * 256), 0));
     };
 
-    f32x16 acc[TM][2];
-    {
-        const f32x16 zacc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    Acc16<Rows> acc[TM];
 #pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) acc[a][b] = zacc;
-    }
-    // this lane's A rows: pixel pi = (wm*TM + tm)*32 + l31 of the tile -> (frame, y, x); sub-tile tm sits a compile-time number of
-    // footprint rows further (S = 8: 4 lines or a whole frame, S = 4: two frames); y & 3 is the same for every tm
-    const int l31 = lane & 31, kh2 = lane >> 5;
-    const int pi0 = wm * (TM * 32) + l31;
+    for (int a = 0; a < TM; ++a) acc_zero(acc[a]);
+    // this lane's A rows: pixel pi = (wm*TM + tm)*32 + Rows::pix(h, lane & 15) of the tile -> (frame, y, x); sub-tile tm sits a
+    // compile-time number of footprint rows further (S = 8: 4 lines or a whole frame, S = 4: two frames; y & 3 is the same for
+    // every tm), fragment 1 one line below fragment 0
+    const int pi0 = wm * (TM * 32) + Rows::pix(0, lane & 15);
     const int f0 = pi0 / SS, y0 = (pi0 % SS) / S, x0 = pi0 % S;
     const int arow0 = f0 * FR + y0 * PITCH + x0;
     auto tmoff = [](int tm) constexpr -> int { return S == 8 ? ((tm >> 1) * FR + (tm & 1) * 4 * PITCH) * 64 : tm * 2 * FR * 64; };
@@ -396,22 +409,22 @@ __device__ __forceinline__ void conv_halo_gbs_tile(const ConvK& p, char* const s
 #endif
     if (nch > 0) {
         unsigned rec = (unsigned)cc_begin * brec + bnt;                 // tap 0 of the first chunk; records are [tap][chunk]
-        bf16x8 bq0[2][2], bq1[2][2];
+        bf16x8 bq0[4], bq1[4];
         dmaH(0, cc_begin);
         ldBq(bq0, rec);
         __builtin_amdgcn_s_waitcnt(0x0070 | (0xf << 8));                // vmcnt(0)
         __builtin_amdgcn_s_barrier();
         int hb = 0, iy = 0, cc = cc_begin;                              // (row loop: see conv_halo_gb_tile)
-        auto row = [&](bf16x8 (&b0)[2][2], bf16x8 (&b1)[2][2]) __attribute__((always_inline)) {
+        auto row = [&](bf16x8 (&b0)[4], bf16x8 (&b1)[4]) __attribute__((always_inline)) {
             const bool first = iy == 0, last = iy == KS - 1, more = cc + 1 < cc_end;
-            const int swz = (y0 + iy) & 3;
+            const int swz[2] = {(y0 + iy) & 3, (y0 + iy + 1) & 3};
             const char* const Arow = hbuf0 + hb * HBYTES + (arow0 + iy * PITCH) * 64;
 #pragma unroll
             for (int ix = 0; ix < KS; ++ix) {
                 const char* const Ah = Arow + ix * 64;
                 auto ldA = [&](int u) __attribute__((always_inline)) -> bf16x8 {
-                    const int kk = u / TM, tm = u % TM, slot = kk * 2 + kh2;
-                    return *reinterpret_cast<const bf16x8*>(Ah + tmoff(tm) + ((slot ^ swz) << 4));
+                    const int tm = u >> 1, h = u & 1;
+                    return *reinterpret_cast<const bf16x8*>(Ah + tmoff(tm) + h * (PITCH * 64) + ((kg ^ swz[h]) << 4));
                 };
                 unsigned nrec = rec + tapstep;
                 if (ix == KS - 1 && last) nrec = more ? (unsigned)(cc + 1) * brec + bnt : rec;
@@ -439,17 +452,20 @@ __device__ __forceinline__ void conv_halo_gbs_tile(const ConvK& p, char* const s
     }
     __syncthreads();
 
-    float* ep = reinterpret_cast<float*>(&smem[0]) + wave * (32 * 64);
-    const int ecol = (lane & 7) * 8, erow = lane >> 3;
+    int te = tid;                                                        // (opaque: see conv_halo_gb_tile)
+    asm volatile("" : "+v"(te));
+    const int elane = te & 63, ewave = te >> 6, ewm = ewave / WN, ewn = ewave % WN;
+    float* ep = reinterpret_cast<float*>(&smem[0]) + ewave * (32 * 64);
+    const int ecol = (elane & 7) * 8, erow = elane >> 3;
     const long long row0 = (long long)ft0 * SS;
-    conv_epilogue<T, TM, DVD_GB_EPI_DEEP>(p, acc, ep, lane, n0 + wn * 64 + ecol, z, ltile, row0, [&](int tm, int j) __attribute__((always_inline)) {
-        const int pi = wm * (TM * 32) + tm * 32 + j * 8 + erow;          // the tile's rows are G consecutive whole frames
+    conv_epilogue<T, TM, DVD_GB_EPI_DEEP>(p, acc, ep, elane, n0 + ewn * 64 + ecol, z, ltile, row0, [&](int tm, int j) __attribute__((always_inline)) {
+        const int pi = ewm * (TM * 32) + tm * 32 + j * 8 + erow;          // the tile's rows are G consecutive whole frames
         return row0 + pi < p.M ? pi : -1;
     });
 }
 
 template <int TM, int S, bool RELU, int KS>
-__global__ __launch_bounds__(256, 2) void conv_halo_gbs_kernel(ConvK p) {
+__global__ __launch_bounds__(256, TM == 2 && S == 8 ? 3 : 2) void conv_halo_gbs_kernel(ConvK p) {
     __shared__ __attribute__((aligned(16))) char smem[HaloGbsCfg<TM, S>::LDSB];
     const int bid = xcd_order(blockIdx.x, gridDim.x);
     const TileMN t = tile_of(p.nmajor, p.tilesN, bid, gridDim.x);
@@ -493,7 +509,7 @@ __device__ __forceinline__ void group_dispatch(const ConvGroup& grp, TileFn fn) 
 }
 
 template <int TM, int WN, int WMV>
-__global__ __launch_bounds__(256, 2) void conv_group_gb_kernel(ConvGroup grp) {
+__global__ __launch_bounds__(256, TM == 2 ? 3 : 2) void conv_group_gb_kernel(ConvGroup grp) {
     __shared__ __attribute__((aligned(16))) char smem[HaloGbCfg<TM, WN, WMV, false>::LDSB];
     group_dispatch(grp, [&](const ConvK& p, int mt, int nt, int z, int t) __attribute__((always_inline)) {
         if (p.kh == 5) conv_halo_gb_tile<TM, WN, WMV, false, false, 5>(p, smem, mt, nt, z, t);
@@ -502,7 +518,7 @@ __global__ __launch_bounds__(256, 2) void conv_group_gb_kernel(ConvGroup grp) {
 }
 
 template <int TM, int S>
-__global__ __launch_bounds__(256, 2) void conv_group_gbs_kernel(ConvGroup grp) {
+__global__ __launch_bounds__(256, TM == 2 && S == 8 ? 3 : 2) void conv_group_gbs_kernel(ConvGroup grp) {
     __shared__ __attribute__((aligned(16))) char smem[HaloGbsCfg<TM, S>::LDSB];
     group_dispatch(grp, [&](const ConvK& p, int mt, int nt, int z, int t) __attribute__((always_inline)) {
         if (p.kh == 5) conv_halo_gbs_tile<TM, S, false, 5>(p, smem, mt, nt, z, t);

@@ -3,10 +3,11 @@ profiles/rNN_pmc_conv.json: per conv launch shape the matrix-pipe occupancy and 
 usage: python tools/pmc_mfma_report.py <rocprof output dir> <out.json> "<command line that was profiled>"
 
 Derivations (MI355X_MICROARCH.md, per-instruction constants): SQ_VALU_MFMA_BUSY_CYCLES counts cycles (32 per
-v_mfma_f32_32x32x16_bf16), summed over the chip's 1024 SIMDs; GRBM_GUI_ACTIVE counts shader-clock cycles while the
+v_mfma_f32_32x32x16_bf16, 16 per v_mfma_f32_16x16x32_bf16: 1024 flop per busy cycle on either), summed over the chip's 1024 SIMDs; GRBM_GUI_ACTIVE counts shader-clock cycles while the
 kernel ran and is reported SUMMED over the 8 XCDs (raw value / duration = 13-14 "GHz"), so it is divided by 8 first.
 pipe_busy = MFMA_BUSY / (1024 * GUI); clock = GUI / kernel duration;
-tflops = INSTS_MFMA * 32768 flop / duration; at_full_pipe = 1024 SIMDs * 1024 flop/cycle * clock."""
+tflops = MFMA_BUSY * 1024 flop / duration; at_full_pipe = 1024 SIMDs * 1024 flop/cycle * clock;
+lds_conflict = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE."""
 import collections
 import csv
 import glob
@@ -40,10 +41,12 @@ for (name, grid, insts), lst in sorted(groups.items(), key=lambda kv: -kv[0][2])
     rows.append({"kernel": name, "grid_threads": grid, "launches": n, "duration_us": round(ns / 1e3, 1),
                  "SQ_INSTS_MFMA": insts, "SQ_VALU_MFMA_BUSY_CYCLES": busy, "SQ_WAVE_CYCLES": avg("SQ_WAVE_CYCLES"),
                  "SQ_BUSY_CYCLES": avg("SQ_BUSY_CYCLES"), "SQ_WAIT_ANY": avg("SQ_WAIT_ANY"),
-                 "SQ_WAIT_INST_ANY": avg("SQ_WAIT_INST_ANY"), "SQ_ACTIVE_INST_ANY": avg("SQ_ACTIVE_INST_ANY"),
+                 "SQ_ACTIVE_INST_ANY": avg("SQ_ACTIVE_INST_ANY"),
+                 "SQ_LDS_BANK_CONFLICT": avg("SQ_LDS_BANK_CONFLICT"), "SQ_LDS_IDX_ACTIVE": avg("SQ_LDS_IDX_ACTIVE"),
                  "GRBM_GUI_ACTIVE_per_xcd": gui,
                  "derived": {"clock_ghz": round(clock, 3), "pipe_busy": round(busy / (1024 * gui), 4) if gui else None,
-                             "tflops": round(insts * 32768 / ns / 1e3, 1) if ns else None,
+                             "tflops": round(busy * 1024 / ns / 1e3, 1) if ns else None,
+                             "lds_conflict": round(avg("SQ_LDS_BANK_CONFLICT") / avg("SQ_LDS_IDX_ACTIVE"), 4) if avg("SQ_LDS_IDX_ACTIVE") else None,
                              "tflops_at_full_pipe_at_this_clock": round(1024 * 1024 * clock / 1e3, 1)}})
 json.dump({"source": cmd, "note": "profiled passes clock lower than un-profiled runs (MI355X_MICROARCH.md, DVFS): compare ratios",
            "launch_shapes": rows}, open(out_path, "w"), indent=1)
