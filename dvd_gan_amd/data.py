@@ -180,29 +180,103 @@ def make_loader(dataset, batch_size, num_workers=0, shuffle=True, device=None, r
     steps_per_epoch / total_step / the log and save cadence of Trainer.train -- is floor(N / B), not ceil(N / B); and in a
     data-parallel run (rank / world given, or read from torch.distributed) every rank iterates ITS OWN 1/world of a common
     permutation (DistributedSampler seeded alike on all ranks; call `loader.set_epoch(e)` per epoch), so an epoch covers
-    the data once instead of world times."""
+    the data once instead of world times.
+    The object has state_dict() / load_state_dict() (the running epoch's record order, the batches yielded, the epoch number): the
+    next `iter()` after load_state_dict() continues that epoch.  With num_workers=0 its first batch is bit-equal to the one the
+    saved loader would have yielded next once Python's `random` is restored too (the global streams are the caller's to save).
+    With num_workers > 0 only the records and their order are promised: crop and flip are drawn in worker processes that
+    DataLoader seeds anew for every iterator."""
     if world is None and torch.distributed.is_available() and torch.distributed.is_initialized():
         world, rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
     sampler = None
     if world is not None and world > 1:
         sampler = data.distributed.DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=shuffle, seed=seed,
                                                       drop_last=True)
-    loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=shuffle and sampler is None, sampler=sampler,
-                             num_workers=num_workers, pin_memory=True, drop_last=True)
+    # the order comes from the sampler DataLoader would have built itself (same draws from the default generator at the same
+    # moment: its __iter__ runs at the first batch); _Resumable lists it, so that the position can be saved
+    base = sampler if sampler is not None else (data.RandomSampler(dataset) if shuffle else data.SequentialSampler(dataset))
+    pos = _EpochPosition(batch_size)
+
+    class _Resumable(data.Sampler):
+        def __len__(self):
+            return len(base)
+
+        def __iter__(self):
+            order, first = pos.begin(lambda: base)
+            yield from order[first * batch_size:]
+
+    loader = data.DataLoader(dataset, batch_size=batch_size, sampler=_Resumable(), num_workers=num_workers, pin_memory=True,
+                             drop_last=True)
 
     class _OnDevice:
         def __len__(self):
             return len(loader)
 
         def set_epoch(self, epoch):
+            pos.epoch = int(epoch)
             if sampler is not None:
                 sampler.set_epoch(epoch)
 
+        def state_dict(self):
+            return pos.state_dict()
+
+        def load_state_dict(self, sd):
+            pos.load_state_dict(sd, len(dataset))
+            if sampler is not None:
+                sampler.set_epoch(pos.epoch)
+
+        def host_batches(self):
+            """(uint8 clips, flips, labels) per batch, still on the host; the position kept as it goes."""
+            if pos.pending:
+                # DataLoader draws a seed for its workers from the default generator whenever an iterator is made; the epoch
+                # that is being continued drew it when it began, so here the generator is left as it was
+                keep = torch.get_rng_state()
+                it = iter(loader)
+                torch.set_rng_state(keep)
+            else:
+                it = iter(loader)
+            for batch in it:
+                pos.cursor += 1
+                yield batch
+
         def __iter__(self):
             dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-            for clips, flips, labels in loader:
+            for clips, flips, labels in self.host_batches():
                 yield clips_to_device(clips, flips, dev), labels
     return _OnDevice()
+
+
+class _EpochPosition:
+    """Where a loader stands inside an epoch: `order`, the record ids of the running epoch as its sampler produced them (never
+    re-derived from a generator state), `cursor`, the batches yielded so far, and `epoch`, the number last given to set_epoch.
+    Plain integers, so a state file holding it loads with weights_only=True."""
+
+    def __init__(self, batch_size):
+        self.batch_size, self.epoch, self.order, self.cursor, self.pending = int(batch_size), 0, None, 0, False
+
+    def begin(self, make_order):
+        """-> (order, batches already yielded) of the epoch to iterate now: the one load_state_dict() left pending, else a new one
+        from make_order()."""
+        if self.pending:
+            self.pending = False
+        else:
+            self.order, self.cursor = [int(i) for i in make_order()], 0
+        return self.order, self.cursor
+
+    def state_dict(self):
+        return {"order": list(self.order or []), "cursor": self.cursor, "epoch": self.epoch, "batch_size": self.batch_size,
+                "started": self.order is not None}
+
+    def load_state_dict(self, sd, n_records):
+        if int(sd["batch_size"]) != self.batch_size:
+            raise ValueError(f"batch_size: the loader state was written with {sd['batch_size']}, this loader has {self.batch_size}")
+        order = [int(i) for i in sd["order"]]
+        if order and not 0 <= min(order) <= max(order) < n_records:
+            raise ValueError(f"order: record ids [{min(order)}, {max(order)}] for a dataset of {n_records} records")
+        if not 0 <= int(sd["cursor"]) <= len(order) // self.batch_size:
+            raise ValueError(f"cursor: {sd['cursor']} batches of {len(order) // self.batch_size} in the saved epoch")
+        self.epoch, self.cursor, self.pending = int(sd["epoch"]), int(sd["cursor"]), bool(sd["started"])
+        self.order = order if self.pending else None
 
 
 # ------------------------------------------------------------------ device-resident clip store
@@ -389,14 +463,29 @@ class StoreLoader:
 
     def __init__(self, store, batch_size, n_frames, crop, shuffle, sampler):
         self.store, self.batch_size, self.n_frames, self.crop, self.shuffle, self.sampler = store, batch_size, n_frames, crop, shuffle, sampler
+        self._pos = _EpochPosition(batch_size)
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else len(self.store)
         return n // self.batch_size
 
     def set_epoch(self, epoch):
+        self._pos.epoch = int(epoch)
         if self.sampler is not None:
             self.sampler.set_epoch(epoch)
+
+    def state_dict(self):
+        """Where iteration stands: the running epoch's record ids in order, the batches already yielded and the epoch number
+        (_EpochPosition).  No random state: `draw` reads Python's `random`, `plan_epoch` torch's default generator -- global
+        streams whoever saves the run saves with it."""
+        return self._pos.state_dict()
+
+    def load_state_dict(self, sd):
+        """The next `iter()` continues the epoch `sd` was taken in: its first batch is the one the saved loader would have
+        yielded next (bit-equal when Python's `random` is restored with it), and `plan_epoch` is not called for that epoch."""
+        self._pos.load_state_dict(sd, len(self.store))
+        if self.sampler is not None:
+            self.sampler.set_epoch(self._pos.epoch)
 
     def plan_epoch(self):
         """The record indices of every batch of one epoch, in order; touches no device.  (Single process with shuffle: draws a
@@ -429,9 +518,19 @@ class StoreLoader:
         frames, boxes, flips, labels = self.draw(record_ids)
         return self.store.gather(record_ids, frames, boxes, flips, self.crop.size), torch.tensor(labels)
 
+    def plans(self):
+        """The host half of one epoch: (record ids, `draw` of them) per batch, the position kept as it goes.  Touches no device.
+        After load_state_dict() it continues the saved epoch instead of planning a new one.  One iteration at a time: the
+        position belongs to the loader, not to the iterator."""
+        order, first = self._pos.begin(lambda: [i for ids in self.plan_epoch() for i in ids])
+        B = self.batch_size
+        for lo in range(first * B, len(order) - B + 1, B):
+            self._pos.cursor += 1
+            yield order[lo:lo + B], self.draw(order[lo:lo + B])
+
     def __iter__(self):
-        for record_ids in self.plan_epoch():
-            yield self.batch(record_ids)
+        for record_ids, (frames, boxes, flips, labels) in self.plans():
+            yield self.store.gather(record_ids, frames, boxes, flips, self.crop.size), torch.tensor(labels)
 
 
 def make_store_loader(store, batch_size, n_frames, sample_size, scales=None, train_crop="corner", shuffle=True, rank=None,

@@ -114,6 +114,98 @@ class FlatAdam:
             self.ema = torch.empty_like(self.flat)
         self.ema.copy_(flat_tensor.reshape(-1))
 
+    # ---- what one step leaves for the next (exact resume: train_step.Trainer.save_state / load_state)
+    def state_dict(self):
+        """Copies of the device tensors and the host scalars one step leaves for the next: flat, m, v, ema (None when none is
+        kept or before the first step), guard_state / guard_ring (None when not allocated), t, lr (param_groups[0]["lr"], what
+        the schedule last set), numel and the settings that decide their shapes and meaning (settings()).  ortho_penalty, a
+        report of the last step, rides along and is never required.  The workspaces are not state.  Copies only, on the
+        current stream; nothing waits for the device."""
+        copy = lambda t: None if t is None else t.detach().clone()
+        sd = {"flat": copy(self.flat), "m": copy(self.m), "v": copy(self.v), "ema": copy(self.ema),
+              "guard_state": copy(self.guard_state), "guard_ring": copy(self.guard_ring), "ortho_penalty": copy(self.ortho_penalty),
+              "t": int(self.t), "lr": float(self.param_groups[0]["lr"]), "numel": int(self.flat.numel())}
+        sd.update(self.settings())
+        return sd
+
+    def settings(self):
+        """The host-side settings of state_dict(), as plain Python values."""
+        return {"betas": [float(b) for b in self.betas], "eps": float(self.eps), "ema_decay": self.ema_decay,
+                "ema_start": self.ema_start, "clip_norm": self.clip_norm, "skip_nonfinite": self.skip_nonfinite,
+                "norm_log": self.norm_log, "ortho": self.ortho}
+
+    def load_state_dict(self, sd):
+        """Copy a state_dict() (tensors on any device) INTO the existing buffers: `flat` is never rebound, so the parameters'
+        .data / .grad views stay what they are.  ema, guard_state and guard_ring are allocated as the first step() would have
+        allocated them.  Raises ValueError naming the field when numel, norm_log (the ring's rows) or the presence of a weight
+        average (ema_decay > 0 against `ema`) disagree with this optimizer.  Settings that only steer future steps (betas, eps,
+        the decay's value, ema_start, clip_norm, skip_nonfinite, ortho) stay as constructed; lr and t are state and are taken
+        from `sd`.  -> list of warning strings, one per setting that differs."""
+        n = self.flat.numel()
+        if int(sd["numel"]) != n:
+            raise ValueError(f"numel: the state holds {int(sd['numel'])} parameters, this optimizer {n}")
+        for k in ("flat", "m", "v"):
+            if sd[k].numel() != n:
+                raise ValueError(f"numel: `{k}` of the state holds {sd[k].numel()} elements, this optimizer {n}")
+        if int(sd["norm_log"]) != self.norm_log:
+            raise ValueError(f"norm_log: the state logs {int(sd['norm_log'])} rows, this optimizer {self.norm_log}")
+        ema, ring, gstate = sd.get("ema"), sd.get("guard_ring"), sd.get("guard_state")
+        if ring is not None and tuple(ring.shape) != (self.norm_log, 4):
+            raise ValueError(f"norm_log: guard_ring of the state is {tuple(ring.shape)}, this optimizer logs {self.norm_log} rows")
+        if bool(float(sd["ema_decay"]) > 0.0) != bool(self.ema_decay) or (ema is not None and not self.ema_decay):
+            raise ValueError(f"ema: the state was written with ema_decay={sd['ema_decay']} "
+                             f"({'a' if ema is not None else 'no'} weight average), this optimizer has ema_decay={self.ema_decay}")
+        if self.ema_decay and ema is None and int(sd["t"]) > 0:
+            raise ValueError(f"ema: the state is {int(sd['t'])} steps old and holds no weight average, this optimizer keeps one")
+        if ema is not None and ema.numel() != n:
+            raise ValueError(f"numel: `ema` of the state holds {ema.numel()} elements, this optimizer {n}")
+        notes = []
+        for k, mine in self.settings().items():
+            theirs = sd.get(k)
+            theirs = [float(b) for b in theirs] if k == "betas" and theirs is not None else theirs
+            if k != "norm_log" and theirs != mine:
+                notes.append(f"{k}: the state was written with {theirs}, this optimizer continues with {mine}")
+        for k in ("flat", "m", "v"):
+            getattr(self, k).copy_(sd[k].reshape(-1))
+        if ema is None:
+            self.ema = None                   # a state from before the first step: step() copies the weights
+        else:
+            self.load_ema(ema)
+        if not self.guard:
+            if gstate is not None:
+                notes.append("guard: the state holds a gradient guard's counters, this optimizer has no guard; they are dropped")
+        elif gstate is None:
+            self.guard_ws = self.guard_state = self.guard_ring = None
+            if int(sd["t"]) > 0:
+                notes.append("guard: the state holds no gradient guard's counters; they start from zero")
+        else:
+            if self.guard_state is None:
+                self._alloc_guard()
+            self.guard_state.copy_(gstate)
+            if self.guard_ring is not None and ring is not None:
+                self.guard_ring.copy_(ring)
+        if self.ortho_penalty is not None and sd.get("ortho_penalty") is not None:
+            self.ortho_penalty.copy_(sd["ortho_penalty"])
+        self.t = int(sd["t"])
+        self.param_groups[0]["lr"] = float(sd["lr"])
+        return notes
+
+    def snapshot_numel(self):
+        """Elements of the slab snapshot_into() fills: numel times 3, or 4 while a weight average exists."""
+        return self.flat.numel() * (3 if self.ema is None else 4)
+
+    def snapshot_into(self, dst):
+        """flat | m | v | ema (when it exists) back to back into `dst`, a flat fp32 tensor on the optimizer's device with at least
+        snapshot_numel() elements: three or four device-to-device copies on the current stream, nothing else.  -> the names of
+        the parts in slab order, each numel elements long."""
+        n, parts = self.flat.numel(), ["flat", "m", "v"] + (["ema"] if self.ema is not None else [])
+        if dst.dtype != torch.float32 or dst.dim() != 1 or dst.device != self.flat.device or dst.numel() < n * len(parts):
+            raise ValueError(f"the slab must be flat fp32 on {self.flat.device} with >= {n * len(parts)} elements, got "
+                             f"{dst.dtype} {tuple(dst.shape)} on {dst.device}")
+        for i, k in enumerate(parts):
+            dst[i * n:(i + 1) * n].copy_(getattr(self, k))
+        return parts
+
     def ortho_grad(self):
         """Add the regularizer's gradient to `grad` (step() does, right before the Adam launch, on the same stream)."""
         if self.ortho_ws is None:
@@ -139,13 +231,16 @@ class FlatAdam:
                 "seen": int(s[K.GUARD_SEEN]), "skipped": int(s[K.GUARD_SKIPPED]), "clipped": int(s[K.GUARD_CLIPPED]),
                 "ring": sorted(rows)}
 
+    def _alloc_guard(self):
+        dev = self.flat.device
+        self.guard_ws = torch.empty(K.grad_guard_ws_bytes(self.grad.numel()), dtype=torch.uint8, device=dev)
+        self.guard_state = torch.zeros(K.GUARD_STATE, dtype=torch.float64, device=dev)
+        if self.norm_log:
+            self.guard_ring = torch.full((self.norm_log, 4), float("nan"), dtype=torch.float64, device=dev)
+
     def _guarded_step(self, ema, decay):
         if self.guard_state is None:
-            dev = self.flat.device
-            self.guard_ws = torch.empty(K.grad_guard_ws_bytes(self.grad.numel()), dtype=torch.uint8, device=dev)
-            self.guard_state = torch.zeros(K.GUARD_STATE, dtype=torch.float64, device=dev)
-            if self.norm_log:
-                self.guard_ring = torch.full((self.norm_log, 4), float("nan"), dtype=torch.float64, device=dev)
+            self._alloc_guard()
         K.grad_guard(self.grad, self.clip_norm or float("inf"), self.skip_nonfinite, self.t, self.guard_ws, self.guard_state,
                      self.guard_ring)
         K.adam_guard_step(self.flat, self.grad, self.m, self.v, ema, self.param_groups[0]["lr"], self.betas[0], self.betas[1],

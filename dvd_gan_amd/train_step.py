@@ -28,6 +28,11 @@ config.sample_step = N > 0 (or the reference's sample_epoch) writes sample sheet
 reference's names, and / or one animated PNG of all clips (config.sample_layout).  `save_predictions` writes real-against-predicted
 comparison sheets of a frame-conditional generator, `save_real` the loader's clips.  None of them leaves a trace in the training
 state or in the default generator.
+config.state_save_step = N > 0 writes the FULL training state every N steps (`save_state`: weights, Adam m / v / t, the weight
+average, the guard's counters, schedules, random streams, loader position; `{step}_state.pt`, the newest config.state_keep kept)
+behind the training loop (checkpoint.StateWriter), and config.resume = a state file or "latest" makes `train()` continue from it:
+the continued run is bit-equal to the run that was never stopped.  `save_models` / config.pretrained_model remain the
+reference-format, weights-only path.
 Out of scope: tensorboard logging, GIF / MP4 files, dataset loaders.
 """
 import contextlib
@@ -67,6 +72,15 @@ class _StepLR:
 
     def get_lr(self):
         return [self.opt.param_groups[0]["lr"]]
+
+    def state_dict(self):
+        return {"kind": self.kind, "n": self.n, "lr": self.opt.param_groups[0]["lr"]}
+
+    def load_state_dict(self, sd):
+        if sd["kind"] != self.kind:
+            raise ValueError(f"lr_schr: the state was written by a {sd['kind']!r} schedule, this one is {self.kind!r}")
+        self.n = int(sd["n"])
+        self.opt.param_groups[0]["lr"] = float(sd["lr"])
 
 
 class _PlateauLR:
@@ -108,6 +122,15 @@ class _PlateauLR:
 
     def get_lr(self):
         return [self.opt.param_groups[0]["lr"]]
+
+    def state_dict(self):
+        return {"kind": "reduce", "best": self.best, "bad": self.bad, "lr": self.opt.param_groups[0]["lr"]}
+
+    def load_state_dict(self, sd):
+        if sd["kind"] != "reduce":
+            raise ValueError(f"lr_schr: the state was written by a {sd['kind']!r} schedule, this one is 'reduce'")
+        self.best, self.bad = float(sd["best"]), int(sd["bad"])
+        self.opt.param_groups[0]["lr"] = float(sd["lr"])
 
 
 class Trainer(object):
@@ -160,6 +183,18 @@ class Trainer(object):
         self.model_save_path = os.path.join(getattr(c, "model_save_path", "./models"), getattr(c, "version", ""))
         self.model_save_epoch = getattr(c, "model_save_epoch", 0)
         self.log_epoch = getattr(c, "log_epoch", 1)
+        # exact resume (all unset = off: no thread, no allocation, no file): a full training state every state_save_step steps
+        # as `{step}_state.pt`, the newest state_keep of them kept (0 = all); resume = a state file or "latest"
+        self.state_save_step = int(getattr(c, "state_save_step", 0) or 0)
+        self.state_keep = int(getattr(c, "state_keep", 2))
+        self.resume = getattr(c, "resume", None) or None
+        if self.state_save_step < 0 or self.state_keep < 0:
+            raise ValueError(f"state_save_step={self.state_save_step}, state_keep={self.state_keep} (both >= 0)")
+        if self.resume and self.pretrained_model:
+            raise ValueError(f"resume={self.resume!r} and pretrained_model={self.pretrained_model!r}: a run continues either from a "
+                             "full training state or from reference-format weights, not from both")
+        self._state_writer = None     # the checkpoint.StateWriter, made at the first save_state()
+        self._resumed_step = None     # the step of the state load_state() read
         # sample sheets (sample_step = sample_epoch = 0: off): period in steps, or in epochs like the reference (trainer.py:186);
         # directory (trainer.py:69); clips per class; "frames" = a PNG per clip, "clips" = one animation of all clips, "both"
         self.sample_step = int(getattr(c, "sample_step", 0) or 0)
@@ -475,7 +510,20 @@ class Trainer(object):
         total_step = self.total_epoch * steps_per_epoch
         start = (self.pretrained_model + 1) if self.pretrained_model else 1
         self._epoch = (start - 1) // max(1, steps_per_epoch)       # a resumed run continues with the epoch it stopped in
-        data_iter = self._new_epoch()
+        data_iter = None
+        state_file = self._resume_file()
+        if state_file is not None:
+            # exact resume: weights, Adam, schedules, random streams and -- where the loader keeps one -- the position inside the
+            # epoch are those of the saved step; the loop goes on with the step after it
+            self.load_state(state_file)
+            start = self._resumed_step + 1
+            if self._loader_resumed:
+                data_iter = iter(self.data_loader)                  # the saved epoch, continued: no new order, no draw
+            else:
+                self._epoch = (start - 1) // max(1, steps_per_epoch)       # a loader without state: its epoch starts over
+        if data_iter is None:
+            data_iter = self._new_epoch()
+        state_save_step = getattr(self, "state_save_step", 0)
         self.D_s.train(); self.D_t.train(); self.G.train()
         t0 = time.time()
         # sample sheets: every sample_step steps, or every sample_epoch epochs (trainer.py:186); 0 = never, nothing is set up
@@ -488,6 +536,8 @@ class Trainer(object):
                     data_iter = self._new_epoch()
                     real_videos, real_labels = next(data_iter)
                 losses = self.train_step(real_videos, real_labels)
+                if state_save_step and step % state_save_step == 0:
+                    self.save_state(step)
                 if self.log_epoch and step % (self.log_epoch * steps_per_epoch) == 0:
                     vals = [float(v.detach()) for v in losses]
                     line = ("Step: [%d/%d], time: %.1fs, ds_loss: %.4f, dt_loss: %.4f, g_s_loss: %.4f, g_t_loss: %.4f, lr: %.2e"
@@ -503,8 +553,158 @@ class Trainer(object):
                     self.save_models(step)
         except BaseException:
             self.close_sheets(quiet=True)          # the loop's exception is the one to report
+            self.close_state(quiet=True)
             raise
         self.close_sheets()
+        self.close_state()
+
+    # ---- exact resume: the full training state (checkpoint.py; DESIGN section 8, "what a step leaves for the next")
+    def _nets(self):
+        return (("G", self.G), ("Ds", self.D_s), ("Dt", self.D_t))
+
+    def _schedulers(self):
+        return (("G", self.g_lr_scher), ("Ds", self.ds_lr_scher), ("Dt", self.dt_lr_scher))
+
+    def fingerprint(self):
+        """The fields that decide shapes and arithmetic (checkpoint.FINGERPRINT): a state continues only a Trainer that agrees
+        in all of them."""
+        c = self.config
+        return {"g_chn": int(self.g_chn), "ds_chn": int(self.ds_chn), "dt_chn": int(self.dt_chn), "n_frames": int(self.n_frames),
+                "n_cond": int(self.n_cond), "n_class": int(self.n_class), "z_dim": int(self.z_dim),
+                "latent_dim": int(self.latent_dim), "g_self_attn": bool(getattr(c, "g_self_attn", False)),
+                "g_sep_attn": bool(getattr(c, "g_sep_attn", False)), "compute_dtype": str(self.compute_dtype),
+                "adv_loss": str(self.adv_loss), "d_iters": int(self.d_iters), "k_sample": int(self.k_sample),
+                "batch_size": int(self.batch_size), "world_size": int(D.world_size()), "dp_mode": str(self.dp_mode)}
+
+    def _resume_file(self):
+        """config.resume -> the state file to continue from, or None (unset, or "latest" with no complete file yet)."""
+        resume = getattr(self, "resume", None)
+        if not resume:
+            return None
+        if resume != "latest":
+            return resume
+        from .checkpoint import latest_state
+        found = latest_state(self.model_save_path)
+        return None if found is None else found[1]
+
+    def _host_state(self):
+        """This process's own host-side state: its random streams (torch's default generator, Python's `random`, numpy's
+        global state, noise_gen) and its loader's position.  The device generator is not in it: nothing in the package draws
+        from it."""
+        from .checkpoint import host_rng_state
+        loader = self.data_loader.state_dict() if hasattr(self.data_loader, "state_dict") else None
+        return {"rng": host_rng_state((("noise_gen", self.noise_gen),)), "loader": loader}
+
+    def save_state(self, step, wait=False):
+        """Write everything step `step` leaves for step + 1 as `{step}_state.pt` under config.model_save_path/version: the
+        three networks' state_dict()s (the trained weights as the optimizers' flat buffers, every other entry by name), the three
+        FlatAdam states (m, v, the weight average, t, lr, the guard's counters and log), the three schedules, step and epoch,
+        the loader's position and the host random streams.  Call it between two train_step() calls, on the stream they are
+        called on.  `load_state` of that file into a Trainer of the same configuration continues the run bit for bit.
+        wait=False: the state is copied device-to-device into a staging slab on the current stream, the host-side state is
+        captured at the same moment, and this call returns; a copy stream takes the slab to pinned memory and a worker thread
+        writes the file (checkpoint.StateWriter, where the memory this costs is stated) -- the calling thread does not wait
+        for the device, and the training step may go on at once.  One snapshot is outstanding at most: a second save_state()
+        first waits for the first file.  wait=True returns when the file is complete.  A file under its final name is complete
+        (written as `.tmp`, fsync'ed, renamed); config.state_keep = n keeps the n newest states.  An exception of the worker is
+        raised by the next save_state() or by close_state().
+        Data parallel: rank 0 writes the file above; every rank writes its own random streams and loader position as
+        `{step}_state.rank{r}.pt`, synchronously (a few kB)."""
+        from . import checkpoint as C
+        folder, step = self.model_save_path, int(step)
+        world, keep = D.world_size(), getattr(self, "state_keep", 2)
+        os.makedirs(folder, exist_ok=True)
+        own = self._host_state()
+        if world > 1:
+            C.atomic_save({"format_version": C.FORMAT_VERSION, "step": step, "rank": self.rank, "host": own},
+                          C.state_path(folder, step, self.rank))
+            if self.rank != 0:
+                return
+        host = {"step": step, "epoch": int(getattr(self, "_epoch", 0)), "opt": {}, "sched": {}, "rng": own["rng"],
+                "loader": own["loader"], "frame_gen": None if self.frame_gen is None else self.frame_gen.get_state().clone()}
+        items, slabs = [], {}
+        copy_of = lambda t: (lambda dst: dst.copy_(t))
+        for tag, net in self._nets():
+            trained = {k for k, p in net.named_parameters() if p.requires_grad}
+            for k, v in net.state_dict().items():
+                if k not in trained:                    # the trained weights are views of the optimizer's `flat`
+                    items.append((f"net.{tag}.{k}", v.dtype, tuple(v.shape), copy_of(v)))
+        for (tag, opt), (_, sched) in zip(self._optimizers(), self._schedulers()):
+            slabs[tag] = (["flat", "m", "v"] + (["ema"] if opt.ema is not None else []), opt.flat.numel())
+            items.append((f"opt.{tag}.slab", torch.float32, (opt.snapshot_numel(),), opt.snapshot_into))
+            for k in ("guard_state", "guard_ring", "ortho_penalty"):
+                t = getattr(opt, k)
+                if t is not None:
+                    items.append((f"opt.{tag}.{k}", t.dtype, tuple(t.shape), copy_of(t)))
+            host["opt"][tag] = dict(opt.settings(), t=int(opt.t), lr=float(opt.param_groups[0]["lr"]), numel=int(opt.flat.numel()))
+            host["sched"][tag] = sched.state_dict()
+        fingerprint = self.fingerprint()
+
+        def make_file(tensors):
+            for tag, (parts, n) in slabs.items():
+                slab = tensors.pop(f"opt.{tag}.slab")
+                for i, k in enumerate(parts):
+                    tensors[f"opt.{tag}.{k}"] = slab[i * n:(i + 1) * n]
+            return {"format_version": C.FORMAT_VERSION, "step": step, "fingerprint": fingerprint, "tensors": tensors, "host": host}
+
+        if self._state_writer is None:
+            self._state_writer = C.StateWriter()
+        self._state_writer.submit(C.state_path(folder, step), items, make_file, device=self.device,
+                                  after=lambda: C.prune_states(folder, keep), wait=wait)
+
+    def close_state(self, quiet=False):
+        """Wait for the state file that is being written and end the writer's thread (a later save_state() starts a new one);
+        its buffers are given back.  An exception the file hit is raised here, unless quiet."""
+        w, self._state_writer = getattr(self, "_state_writer", None), None
+        if w is not None:
+            try:
+                w.close()
+            except Exception:
+                if not quiet:
+                    raise
+
+    def load_state(self, path):
+        """Continue from the file save_state() wrote: copies every tensor into the existing buffers (no parameter is rebound),
+        sets the optimizers' t / lr, the schedules, step and epoch, the loader's position (when the loader has
+        load_state_dict()) and the host random streams.  Read with weights_only=True.  ValueError naming the field on an
+        unknown format_version, on the first fingerprint field that differs, and on a tensor that is missing or of another
+        shape.  In a data-parallel run every rank reads this file and its own `{step}_state.rank{r}.pt` next to it.  -> list of
+        warning strings (settings that only steer future steps and differ from the file's; the constructor's hold)."""
+        from . import checkpoint as C
+        sd = C.load_file(path)
+        C.check_fingerprint(sd["fingerprint"], self.fingerprint())
+        tensors, host, step = sd["tensors"], sd["host"], int(sd["step"])
+        own = host
+        if D.world_size() > 1:
+            rank_file = C.state_path(os.path.dirname(path), step, self.rank)
+            own = C.load_file(rank_file)["host"]
+        for tag, net in self._nets():
+            trained = {k for k, p in net.named_parameters() if p.requires_grad}
+            for k, v in net.state_dict().items():
+                if k in trained:
+                    continue
+                src = tensors.get(f"net.{tag}.{k}")
+                if src is None or tuple(src.shape) != tuple(v.shape) or src.dtype != v.dtype:
+                    raise ValueError(f"net.{tag}.{k}: the state holds {None if src is None else (src.dtype, tuple(src.shape))}, "
+                                     f"the network {(v.dtype, tuple(v.shape))}")
+                v.copy_(src)
+        notes = []
+        for (tag, opt), (_, sched) in zip(self._optimizers(), self._schedulers()):
+            osd = dict(host["opt"][tag])
+            for k in ("flat", "m", "v", "ema", "guard_state", "guard_ring", "ortho_penalty"):
+                osd[k] = tensors.get(f"opt.{tag}.{k}")
+            if osd["flat"] is None or osd["m"] is None or osd["v"] is None:
+                raise ValueError(f"opt.{tag}: the state holds no flat / m / v for this optimizer")
+            notes += [f"{tag}: {n}" for n in opt.load_state_dict(osd)]
+            sched.load_state_dict(host["sched"][tag])
+        self._epoch, self._resumed_step = int(host["epoch"]), step
+        self._loader_resumed = own.get("loader") is not None and hasattr(self.data_loader, "load_state_dict")
+        if self._loader_resumed:
+            self.data_loader.load_state_dict(own["loader"])
+        if self.frame_gen is not None and host.get("frame_gen") is not None:
+            self.frame_gen.set_state(host["frame_gen"])
+        C.set_host_rng_state(own["rng"], (("noise_gen", self.noise_gen),))
+        return notes
 
     # ---- trainer.py:195-197, 323-334, 389-391: sample sheets (sheets.py)
     def fixed_inputs(self):
