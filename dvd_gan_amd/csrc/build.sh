@@ -1,5 +1,5 @@
 #!/bin/bash
-# Builds libdvdgan_hip.so for gfx950 (cross-compiles without a GPU).  Usage: build.sh [-j N]
+# Builds libdvdgan_hip.so and libdvdgan_hip_adv.so for gfx950 (cross-compiles without a GPU).  Usage: build.sh [-j N]
 # Every compile also leaves build/<file>.res = hipcc's kernel-resource-usage remarks (registers, spills, scratch per kernel):
 # tests/test_abi_cpu.py holds the hot kernels to "no scratch" with it (a dynamically indexed accumulator array once put every
 # convolution kernel's accumulators into scratch memory: 3x on the step, invisible to every parity test).
@@ -23,3 +23,16 @@ done
 for p in "${pids[@]}"; do wait "$p"; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o libdvdgan_hip.so build/*.o
 echo "built $(pwd)/libdvdgan_hip.so"
+# libdvdgan_hip_adv.so (include/dvdgan_hip_adv.h): a library of its own, so its objects stay out of build/*.o
+mkdir -p adv/build
+for f in adv/*.hip; do
+  o=adv/build/$(basename "${f%.hip}").o
+  r=adv/build/$(basename "${f%.hip}").res
+  if [ ! -f "$o" ] || [ ! -f "$r" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ ../../include/dvdgan_hip.h -nt "$o" ] || [ ../../include/dvdgan_hip_adv.h -nt "$o" ]; then
+    hipcc $FLAGS -c "$f" -o "$o" 2> "$r.tmp" || { cat "$r.tmp" >&2; rm -f "$o" "$r.tmp"; exit 1; }
+    grep -v "remark:\|^ *[0-9]* |\|^ *| *^" "$r.tmp" >&2 || true
+    grep "remark:" "$r.tmp" > "$r" || true; rm -f "$r.tmp"
+  fi
+done
+hipcc --offload-arch=gfx950 -shared -fPIC -o libdvdgan_hip_adv.so adv/build/*.o
+echo "built $(pwd)/libdvdgan_hip_adv.so"

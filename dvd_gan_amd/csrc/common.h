@@ -73,6 +73,19 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// sum over the workgroup (blockDim.x <= 1024; sh: 32 floats of LDS), result broadcast.  Shared by misc.hip and adv/adv_loss_ex.hip, so
+// the two adversarial-loss kernels reduce in the same order
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+    v = wave_sum(v);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if (l == 0) sh[w] = v;
+    __syncthreads();
+    float t = (threadIdx.x < nw) ? sh[threadIdx.x] : 0.f;
+    if (w == 0) { t = wave_sum(t); if (l == 0) sh[0] = t; }
+    __syncthreads();
+    return sh[0];
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

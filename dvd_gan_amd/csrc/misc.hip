@@ -5,18 +5,6 @@
 
 namespace {
 
-__device__ float block_sum(float v, float* sh) {          // blockDim.x <= 1024, result broadcast
-    v = wave_sum(v);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
-    if (l == 0) sh[w] = v;
-    __syncthreads();
-    float t = (threadIdx.x < nw) ? sh[threadIdx.x] : 0.f;
-    if (w == 0) { t = wave_sum(t); if (l == 0) sh[0] = t; }
-    __syncthreads();
-    return sh[0];
-}
-
 // ----------------------------------------------------------------------------- spectral norm
 // Normalization.py:19-31 -- one power iteration on W [h][w]:
 //   v <- W^T u / (|W^T u| + eps);  u <- W v / (|W v| + eps);  sigma = u . (W v)

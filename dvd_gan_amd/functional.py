@@ -942,6 +942,31 @@ class AdvLoss(Function):
         return dout * g, None, None
 
 
+class AdvLossEx(Function):
+    """AdvLoss with the stabilisers that work on the logits alone (dvd_adv_loss_ex, one launch; libdvdgan_hip_adv.so) -> the adversarial term.
+    group: logits per sample (out is sample-major); keep: samples whose logits carry the adversarial gradient (0 = all);
+    lecam: strength of the LeCam gradient (0 = off).  anchors: None, or (other, prev, next, decay) -- one-float device views:
+    the other kind's anchor and this kind's of the previous slot, this kind's of the current slot, which is written.
+    stats: None or a float32 [lib.ADV_NSTAT] device view, overwritten.  Nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, out, real_flag, hinge, group, keep, lecam, anchors, stats):
+        out = out.contiguous()
+        loss = torch.zeros(1, dtype=torch.float32, device=out.device)
+        dout = torch.empty_like(out)
+        other, prev, nxt, decay = anchors if anchors is not None else (None, None, None, 0.0)
+        L.check(L.adv_lib().dvd_adv_loss_ex(L.ptr(out), out.numel(), int(group), int(hinge), int(real_flag), int(keep), float(lecam),
+                                            L.ptr(other), L.ptr(prev), L.ptr(nxt), float(decay), L.ptr(loss), L.ptr(dout), 1.0,
+                                            L.ptr(stats), L.stream()))
+        ctx.save_for_backward(dout)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dout,) = ctx.saved_tensors
+        return dout * g, None, None, None, None, None, None, None
+
+
 # ------------------------------------------------------------------ reference-layout helpers
 class VidDownsample(Function):
     """utils.py:77-83"""

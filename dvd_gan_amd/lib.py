@@ -180,6 +180,39 @@ def lib():
     return _lib
 
 
+# ---- libdvdgan_hip_adv.so (include/dvdgan_hip_adv.h): the loss launch with LeCam regularization, top-k selection and logit
+# statistics, a library of its own with the same handshake -- every `#define DVD_ADV_*` of its header by name, one line of
+# type codes per entry point (tests/test_adv_ref_cpu.py compares both with the header and the exports with the table)
+ADV_MAX_SAMPLES, ADV_NSTAT = 4096, 8        # samples a selection serves, floats of the statistics
+(ADV_STAT_MEAN, ADV_STAT_SIGN, ADV_STAT_ACTIVE, ADV_STAT_ADV, ADV_STAT_LECAM, ADV_STAT_ANCHOR, ADV_STAT_KEPT,
+ ADV_STAT_NONFINITE) = range(ADV_NSTAT)
+ADV_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
+                        if name.startswith("ADV_") and isinstance(value, int)}
+ADV_SIGNATURES = {
+    "dvd_adv_loss_ex": "i p l iiii f ppp f pp f p p",
+}
+ADV_LIB_PATH = os.environ.get("DVD_ADV_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_adv.so")
+_adv_lib = None
+
+
+def adv_lib():
+    """The loaded libdvdgan_hip_adv.so, typed from ADV_SIGNATURES.  Raises (never falls back) when it has not been built."""
+    global _adv_lib
+    if _adv_lib is None:
+        if not os.path.exists(ADV_LIB_PATH):
+            raise RuntimeError(
+                f"{ADV_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(dvd_gan_amd has no CPU / eager fallback)")
+        loaded = C.CDLL(ADV_LIB_PATH)
+        for name, sig in ADV_SIGNATURES.items():
+            fn = getattr(loaded, name, None)
+            if fn is None:
+                raise RuntimeError(f"libdvdgan_hip_adv.so exports no {name} -- lib.py and include/dvdgan_hip_adv.h disagree")
+            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
+        _adv_lib = loaded
+    return _adv_lib
+
+
 ABI_VERSION = 13
 
 

@@ -33,6 +33,10 @@ average, the guard's counters, schedules, random streams, loader position; `{ste
 behind the training loop (checkpoint.StateWriter), and config.resume = a state file or "latest" makes `train()` continue from it:
 the continued run is bit-equal to the run that was never stopped.  `save_models` / config.pretrained_model remain the
 reference-format, weights-only path.
+config.lecam = lambda > 0 adds LeCam regularization (Tseng et al. 2021) to the discriminators' gradients, config.g_topk = nu > 0
+lets the generator step take gradient only from the samples each discriminator scores highest (Sinha et al. 2020), config.d_stats
+keeps logit statistics, among them the overfitting indicator r_t = E[sign D(real)] (Karras et al. 2020): all inside the loss
+launch (functional.AdvLossEx), nothing read back; `d_stats()` is the one call that synchronizes.
 Out of scope: tensorboard logging, GIF / MP4 files, dataset loaders.
 """
 import contextlib
@@ -133,6 +137,13 @@ class _PlateauLR:
         self.opt.param_groups[0]["lr"] = float(sd["lr"])
 
 
+def topk_keep(batch, nu, gamma, epoch):
+    """Samples the generator step keeps in `epoch` (0-based): max(ceil(nu * B), floor(B * gamma^epoch)), annealed from the whole
+    batch down to the floor nu (Sinha et al. 2020), never below 1 or above B."""
+    import math
+    return max(1, min(int(batch), max(math.ceil(nu * batch), math.floor(batch * gamma ** epoch))))
+
+
 class Trainer(object):
     def __init__(self, data_loader, config, device=None, compute_dtype=torch.bfloat16, latent_dim=4, dp_mode="replica"):
         """dp_mode (data-parallel runs only): "replica" = per-replica batch-norm statistics and condition rows, the
@@ -178,6 +189,25 @@ class Trainer(object):
         if not (0.0 <= self.g_clip_norm < float("inf") and 0.0 <= self.d_clip_norm < float("inf")) or self.grad_log < 0:
             raise ValueError(f"g_clip_norm={self.g_clip_norm}, d_clip_norm={self.d_clip_norm} (finite norms >= 0), "
                              f"grad_log={self.grad_log} (rows >= 0)")
+        # stabilisers and diagnostics on the discriminators' logits (all 0 / False = off: calc_loss is then the plain launch).
+        # LeCam regularization: strength, decay of the logit anchors, first D iteration the gradient applies in (the anchors
+        # accumulate from the first one); top-k generator updates: floor nu of the kept fraction, its decay per epoch; the
+        # logit statistics behind d_stats()
+        self.lecam = float(getattr(c, "lecam", 0.0))
+        self.lecam_decay = float(getattr(c, "lecam_decay", 0.99))
+        self.lecam_start = int(getattr(c, "lecam_start", 0))
+        self.g_topk = float(getattr(c, "g_topk", 0.0))
+        self.g_topk_decay = float(getattr(c, "g_topk_decay", 0.99))
+        self._d_stats_on = bool(getattr(c, "d_stats", False))
+        if (not 0.0 <= self.lecam < float("inf") or not 0.0 <= self.lecam_decay < 1.0 or self.lecam_start < 0
+                or not 0.0 <= self.g_topk <= 1.0 or not 0.0 < self.g_topk_decay <= 1.0):
+            raise ValueError(f"lecam={self.lecam} (finite, >= 0), lecam_decay={self.lecam_decay} (in [0, 1)), "
+                             f"lecam_start={self.lecam_start} (>= 0), g_topk={self.g_topk} (in [0, 1]), "
+                             f"g_topk_decay={self.g_topk_decay} (in (0, 1])")
+        self._adv_ex = self.lecam > 0.0 or self.g_topk > 0.0 or self._d_stats_on
+        self._anchors = None          # fp32 [2 slots][D_s, D_t][real, fake] on the device, when lecam > 0
+        self._adv_stats = None        # fp32 [6][lib.ADV_NSTAT]: D_s real / fake, D_t real / fake, G step D_s / D_t
+        self._lecam_it = 0            # D iterations done
         self.lr_decay = getattr(c, "lr_decay", 0.9999)
         self.pretrained_model = getattr(c, "pretrained_model", None)
         self.model_save_path = os.path.join(getattr(c, "model_save_path", "./models"), getattr(c, "version", ""))
@@ -214,6 +244,10 @@ class Trainer(object):
         self._sheets = None           # the sheets.SheetWriter, made at first use
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.compute_dtype, self.latent_dim = compute_dtype, latent_dim
+        if self._adv_ex:
+            self._adv_stats = torch.zeros(6, L.ADV_NSTAT, dtype=torch.float32, device=self.device)
+            if self.lecam > 0.0:
+                self._anchors = torch.zeros(2, 2, 2, dtype=torch.float32, device=self.device)
         Fn.direct_weight_grads(True)          # weight gradients accumulate into FlatAdam's buffers on a side stream
         self.exchange = GradExchange()
         # The step's dependent chain runs on a high-priority stream (ahead of the bulk weight-gradient stream) -- in a
@@ -330,8 +364,62 @@ class Trainer(object):
         self._plateau = not isinstance(self.g_lr_scher, _StepLR)
 
     # ---- trainer.py:114-121
-    def calc_loss(self, x, real_flag):
-        return Fn.AdvLoss.apply(x, bool(real_flag), self.adv_loss == "hinge")
+    def calc_loss(self, x, real_flag, _site=None):
+        """_site (passed by _train_step alone, and only when a stabiliser or the statistics are on): row of the statistics
+        table -- 0 / 1 D_s real / fake, 2 / 3 D_t real / fake, 4 / 5 the generator step's D_s / D_t."""
+        if _site is None or not getattr(self, "_adv_ex", False):
+            return Fn.AdvLoss.apply(x, bool(real_flag), self.adv_loss == "hinge")
+        group = x.numel() // self._cur_B               # k_sample for D_s, frames / 4 for D_t: the logits are sample-major
+        keep, lecam, anchors = 0, 0.0, None
+        if _site >= 4:
+            if self.g_topk > 0.0:                      # (train() counts the epochs it has started: the running one is _epoch - 1)
+                keep = topk_keep(self._cur_B, self.g_topk, self.g_topk_decay, max(0, getattr(self, "_epoch", 0) - 1))
+                keep = 0 if keep >= self._cur_B else keep          # the whole batch: the same arithmetic without the ranking
+        elif self._anchors is not None:
+            # iteration `it` reads the anchors of slot (it - 1) & 1 and writes slot it & 1: the real and the fake call of a network
+            # touch different floats and neither depends on the other's order (the real pass may run early on a side stream)
+            it, net, kind = self._lecam_it, _site // 2, _site % 2
+            prev, cur = self._anchors[(it - 1) & 1, net], self._anchors[it & 1, net]
+            anchors = (prev[1 - kind:2 - kind], prev[kind:kind + 1], cur[kind:kind + 1], self.lecam_decay if it else 0.0)
+            lecam = self.lecam if it >= self.lecam_start else 0.0
+        return Fn.AdvLossEx.apply(x, bool(real_flag), self.adv_loss == "hinge", group, keep, lecam, anchors,
+                                  self._adv_stats[_site])
+
+    def _site_loss(self, x, real_flag, site):
+        return self.calc_loss(x, real_flag, _site=site) if getattr(self, "_adv_ex", False) else self.calc_loss(x, real_flag)
+
+    def _end_d_iteration(self):
+        """The anchors of the slot this D iteration wrote become those of the global batch (the update is linear in the batch
+        mean and the shards are equal): one all-reduce of 4 floats, only in a data-parallel run."""
+        if getattr(self, "_anchors", None) is None:
+            return
+        if self.exchange.active:
+            cur = self._anchors[self._lecam_it & 1]
+            buf = cur.to(D.collective_device())
+            torch.distributed.all_reduce(buf, op=torch.distributed.ReduceOp.SUM)
+            cur.copy_(buf / D.world_size())
+        self._lecam_it += 1
+
+    def d_stats(self):
+        """The logit statistics of the last step as a host dict, or None when lecam, g_topk and d_stats are all off.  The one
+        call of this group that synchronizes.  Per discriminator: r_t = E[sign D(real)] (Karras et al. 2020: near 1 means D has
+        memorised the training set), the mean logits, the hinge-active fractions, the LeCam penalties and the anchors they were
+        measured against, the count of non-finite logits; and the samples the generator step kept."""
+        if self._adv_stats is None:
+            return None
+        s = self._adv_stats.cpu().tolist()
+        a = None if self._anchors is None else self._anchors[(self._lecam_it - 1) & 1].cpu().tolist()
+        out = {"it": self._lecam_it}
+        for net, tag in enumerate(("Ds", "Dt")):
+            real, fake, g = s[2 * net], s[2 * net + 1], s[4 + net]
+            out[tag] = {"r_t": real[L.ADV_STAT_SIGN], "sign_fake": fake[L.ADV_STAT_SIGN],
+                        "mean_real": real[L.ADV_STAT_MEAN], "mean_fake": fake[L.ADV_STAT_MEAN],
+                        "active_real": real[L.ADV_STAT_ACTIVE], "active_fake": fake[L.ADV_STAT_ACTIVE],
+                        "lecam_real": real[L.ADV_STAT_LECAM], "lecam_fake": fake[L.ADV_STAT_LECAM],
+                        "anchor_real": None if a is None else a[net][0], "anchor_fake": None if a is None else a[net][1],
+                        "nonfinite": real[L.ADV_STAT_NONFINITE] + fake[L.ADV_STAT_NONFINITE] + g[L.ADV_STAT_NONFINITE],
+                        "g_kept": int(g[L.ADV_STAT_KEPT]), "g_mean": g[L.ADV_STAT_MEAN]}
+        return out
 
     # ---- trainer.py:84-88
     def label_sample(self):
@@ -402,6 +490,7 @@ class Trainer(object):
         real_videos = to_device_async(real_videos, self.device).permute(0, 2, 1, 3, 4).contiguous()
         real_labels = to_device_async(self._check_labels(real_labels), self.device)
         T, k, Kc = self.n_frames, self.k_sample, self.n_cond
+        self._cur_B = real_videos.shape[0]
         cond = real_videos[:, :Kc].contiguous() if Kc else None       # [B,K,3,H,W] context frames; the targets follow them
         ex = self.exchange
         fg = self.frame_gen
@@ -424,9 +513,9 @@ class Trainer(object):
                 cur = torch.cuda.current_stream()
                 self._aux.wait_stream(cur)
                 with torch.cuda.stream(self._aux):
-                    ds_loss_real = self.calc_loss(self.D_s(real_s, real_labels), True)
+                    ds_loss_real = self._site_loss(self.D_s(real_s, real_labels), True, 0)
                     real_d = vid_downsample(real_videos)
-                    dt_loss_real = self.calc_loss(self.D_t(real_d, real_labels), True)
+                    dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
                 for t_ in (real_s, real_videos, real_labels):
                     t_.record_stream(self._aux)
             fake_videos = self.G(z, z_class, hidden, cond=cond)
@@ -438,8 +527,8 @@ class Trainer(object):
                 for t_ in (ds_loss_real, dt_loss_real, real_d):
                     t_.record_stream(cur)
             else:
-                ds_loss_real = self.calc_loss(self.D_s(real_s, real_labels), True)
-            ds_loss_fake = self.calc_loss(self.D_s(fake_s.detach(), z_class), False)
+                ds_loss_real = self._site_loss(self.D_s(real_s, real_labels), True, 0)
+            ds_loss_fake = self._site_loss(self.D_s(fake_s.detach(), z_class), False, 1)
             self.reset_grad()
             (ds_loss_real + ds_loss_fake).backward()
             Fn.join_side()
@@ -448,8 +537,8 @@ class Trainer(object):
             fake_d = vid_downsample(fake_videos) if cond is None else vid_downsample_cat(cond, fake_videos)
             if not early:
                 real_d = vid_downsample(real_videos)
-                dt_loss_real = self.calc_loss(self.D_t(real_d, real_labels), True)
-            dt_loss_fake = self.calc_loss(self.D_t(fake_d.detach(), z_class), False)
+                dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
+            dt_loss_fake = self._site_loss(self.D_t(fake_d.detach(), z_class), False, 3)
             ex.finish("Ds")
             self.ds_optimizer.step()
             self.ds_lr_scher.step((ds_loss_real + ds_loss_fake) if self._plateau else None)
@@ -457,6 +546,7 @@ class Trainer(object):
             (dt_loss_real + dt_loss_fake).backward()
             Fn.join_side()
             ex.start("Dt", self.dt_optimizer.grad)
+            self._end_d_iteration()
             last = _ == self.d_iters - 1
             if not last:
                 ex.finish("Dt")
@@ -465,11 +555,11 @@ class Trainer(object):
         # ---------------- G, through the updated discriminators, weights of D held constant.  The D_t gradient exchange
         # of the last D iteration overlaps the D_s forward (D_s is already updated; D_t's update waits for the exchange)
         self._freeze_d(True)
-        g_s_loss = self.calc_loss(self.D_s(fake_s, z_class), True)
+        g_s_loss = self._site_loss(self.D_s(fake_s, z_class), True, 4)
         ex.finish("Dt")
         self.dt_optimizer.step()
         self.dt_lr_scher.step((dt_loss_real + dt_loss_fake) if self._plateau else None)
-        g_t_loss = self.calc_loss(self.D_t(fake_d, z_class), True)
+        g_t_loss = self._site_loss(self.D_t(fake_d, z_class), True, 5)
         self._freeze_d(False)
         self.g_optimizer.zero_grad()
         if ex.active:
@@ -546,6 +636,10 @@ class Trainer(object):
                     for tag, rep in (self.guard_report() or {}).items():
                         if rep is not None:
                             line += ", %s |g|: %.3e skipped: %d" % (tag, rep["norm"], rep["skipped"])
+                    rep = self.d_stats() if getattr(self, "_adv_stats", None) is not None else None
+                    for tag in ("Ds", "Dt") if rep else ():
+                        line += ", %s r_t: %.3f lecam: %.3e/%.3e" % (tag, rep[tag]["r_t"], rep[tag]["lecam_real"],
+                                                                     rep[tag]["lecam_fake"])
                     print(line)
                 if sample_step and step % sample_step == 0:
                     self.save_samples(step)
@@ -638,6 +732,10 @@ class Trainer(object):
                     items.append((f"opt.{tag}.{k}", t.dtype, tuple(t.shape), copy_of(t)))
             host["opt"][tag] = dict(opt.settings(), t=int(opt.t), lr=float(opt.param_groups[0]["lr"]), numel=int(opt.flat.numel()))
             host["sched"][tag] = sched.state_dict()
+        if getattr(self, "_anchors", None) is not None:       # LeCam: both slots of each discriminator's anchors and the count
+            for net, tag in enumerate(("Ds", "Dt")):
+                items.append((f"lecam.{tag}", torch.float32, (2, 2), copy_of(self._anchors[:, net])))
+            host["lecam_it"] = int(self._lecam_it)
         fingerprint = self.fingerprint()
 
         def make_file(tensors):
@@ -697,6 +795,16 @@ class Trainer(object):
                 raise ValueError(f"opt.{tag}: the state holds no flat / m / v for this optimizer")
             notes += [f"{tag}: {n}" for n in opt.load_state_dict(osd)]
             sched.load_state_dict(host["sched"][tag])
+        if getattr(self, "_anchors", None) is not None:
+            saved = [tensors.get(f"lecam.{tag}") for tag in ("Ds", "Dt")]
+            if any(t is None or tuple(t.shape) != (2, 2) for t in saved) or "lecam_it" not in host:
+                self._anchors.zero_()
+                self._lecam_it = 0
+                notes.append("lecam: the state holds no anchors (it was written with lecam off): they start afresh")
+            else:
+                for net, t in enumerate(saved):
+                    self._anchors[:, net].copy_(t)
+                self._lecam_it = int(host["lecam_it"])
         self._epoch, self._resumed_step = int(host["epoch"]), step
         self._loader_resumed = own.get("loader") is not None and hasattr(self.data_loader, "load_state_dict")
         if self._loader_resumed:
