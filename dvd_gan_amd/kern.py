@@ -657,3 +657,73 @@ def sample_sheet(src, strides, n_sheets, n_tiles, H, W, first_slot, total_slots,
                                      int(W), int(first_slot), int(total_slots), int(nrow), int(padding), float(pad_value),
                                      int(row_prefix), int(flags), L.ptr(dst), L.stream()))
     return dst
+
+
+# ------------------------------------------------------------------ libdvdgan_hip_eval.so: distribution distances (distmetrics.py)
+def _rows_f32(x, what):
+    """(tensor, rows, d, row stride) of a device fp32 matrix whose rows are contiguous (a column slice of a wider matrix is served
+    without a copy; anything else is made contiguous)."""
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError(f"{what} must be a device fp32 matrix [rows, d], got {tuple(x.shape)} {x.dtype} on {x.device}")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{what} is empty: {tuple(x.shape)}")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x, x.shape[0], x.shape[1], (x.stride(0) if x.shape[0] > 1 else x.shape[1])
+
+
+def eval_pool_features(act, group=1):
+    """dvd_eval_pool_features: channels-last activation [R, *spatial, C] (bf16 / fp32) -> fp32 [R / group, C], the mean over
+    `group` consecutive rows of sum_positions relu(act)."""
+    act = act.contiguous()
+    R, Cc = act.shape[0], act.shape[-1]
+    P = act.numel() // max(R * Cc, 1)
+    group = int(group)
+    if group < 1 or R % group:
+        raise ValueError(f"group={group} does not divide the {R} rows of the activation")
+    out = torch.empty(R // group, Cc, dtype=torch.float32, device=act.device)
+    L.eval_check(L.eval_lib().dvd_eval_pool_features(L.dt(act), L.ptr(act), R, P, Cc, group, L.ptr(out), L.stream()))
+    return out
+
+
+def eval_moments_state(d, device):
+    """(pivot fp32 [d], state fp64 [S1 | upper-triangular tiles of S2]) for dvd_eval_moments_update; the first update fills both."""
+    nd = L.eval_lib().dvd_eval_moments_state_doubles(int(d))
+    if nd < 0:
+        raise ValueError(f"feature width d={d} outside [1, {L.EVAL_MAX_D}]")
+    return torch.empty(int(d), dtype=torch.float32, device=device), torch.empty(nd, dtype=torch.float64, device=device)
+
+
+def eval_moments_update(x, pivot, state, first):
+    """dvd_eval_moments_update: adds the rows of x [n, d] (device fp32, row stride >= d) to the running state; no host sync."""
+    x, n, d, ld = _rows_f32(x, "features")
+    assert pivot.numel() == d and pivot.dtype == torch.float32 and state.dtype == torch.float64
+    L.eval_check(L.eval_lib().dvd_eval_moments_update(x.data_ptr(), n, d, ld, L.ptr(pivot), L.ptr(state), int(bool(first)),
+                                                      L.stream()))
+
+
+def eval_kid(x, y, ix, iy):
+    """dvd_eval_kid: x [n, d], y [m, d] device fp32; ix, iy host int32 [n_sub, s] row tables -> (values fp64 [n_sub], terms fp64
+    [n_sub, 3]) on the device.  The tables are range-checked on the host and uploaded once."""
+    x, n, d, ldx = _rows_f32(x, "x")
+    y, m, d2, ldy = _rows_f32(y, "y")
+    if d != d2 or x.device != y.device:
+        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} must share the feature width and the device")
+    ix = torch.as_tensor(ix, dtype=torch.int32).contiguous()
+    iy = torch.as_tensor(iy, dtype=torch.int32).contiguous()
+    if ix.dim() != 2 or ix.shape != iy.shape or ix.is_cuda or iy.is_cuda:
+        raise ValueError(f"index tables must be host [n_sub, s] of one shape, got {tuple(ix.shape)} / {tuple(iy.shape)}")
+    n_sub, s = ix.shape
+    lib = L.eval_lib()
+    nws = lib.dvd_eval_kid_ws_doubles(n_sub, s)
+    if nws < 0:
+        L.eval_check(int(nws))
+    tab = torch.stack([ix, iy])
+    tab_d = tab.to(x.device, non_blocking=False)
+    ws = torch.empty(nws, dtype=torch.float64, device=x.device)
+    out = torch.empty(n_sub, dtype=torch.float64, device=x.device)
+    terms = torch.empty(n_sub, 3, dtype=torch.float64, device=x.device)
+    L.eval_check(lib.dvd_eval_kid(x.data_ptr(), n, ldx, y.data_ptr(), m, ldy, d, tab[0].data_ptr(), tab[1].data_ptr(),
+                                  tab_d[0].data_ptr(), tab_d[1].data_ptr(), n_sub, s, L.ptr(ws), L.ptr(out), L.ptr(terms),
+                                  L.stream()))
+    return out, terms

@@ -213,6 +213,47 @@ def adv_lib():
     return _adv_lib
 
 
+# ---- libdvdgan_hip_eval.so (include/dvdgan_hip_eval.h): pooled features, running moments and kernel distances of sample
+# features (distmetrics.py), the third library with the same handshake (tests/test_distmetrics_cpu.py compares the constants and
+# the table with the header and the exports with the table)
+EVAL_MAX_D, EVAL_TILE, EVAL_MAX_SUBSETS = 4096, 64, 65535
+EVAL_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
+                         if name.startswith("EVAL_") and isinstance(value, int)}
+EVAL_SIGNATURES = {
+    "dvd_eval_strerror": "s i",
+    "dvd_eval_pool_features": "i ip liii p p",
+    "dvd_eval_moments_state_doubles": "l i",
+    "dvd_eval_moments_update": "i p lil pp i p",
+    "dvd_eval_kid_ws_doubles": "l ii",
+    "dvd_eval_kid": "i pll pll i pppp ii ppp p",
+}
+EVAL_LIB_PATH = os.environ.get("DVD_EVAL_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_eval.so")
+_eval_lib = None
+
+
+def eval_lib():
+    """The loaded libdvdgan_hip_eval.so, typed from EVAL_SIGNATURES.  Raises (never falls back) when it has not been built."""
+    global _eval_lib
+    if _eval_lib is None:
+        if not os.path.exists(EVAL_LIB_PATH):
+            raise RuntimeError(
+                f"{EVAL_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(dvd_gan_amd has no CPU / eager fallback)")
+        loaded = C.CDLL(EVAL_LIB_PATH)
+        for name, sig in EVAL_SIGNATURES.items():
+            fn = getattr(loaded, name, None)
+            if fn is None:
+                raise RuntimeError(f"libdvdgan_hip_eval.so exports no {name} -- lib.py and include/dvdgan_hip_eval.h disagree")
+            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
+        _eval_lib = loaded
+    return _eval_lib
+
+
+def eval_check(code):
+    if code != 0:
+        raise RuntimeError(f"libdvdgan_hip_eval: {eval_lib().dvd_eval_strerror(code).decode()} (code {code})")
+
+
 ABI_VERSION = 13
 
 

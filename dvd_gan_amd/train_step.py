@@ -37,6 +37,10 @@ config.lecam = lambda > 0 adds LeCam regularization (Tseng et al. 2021) to the d
 lets the generator step take gradient only from the samples each discriminator scores highest (Sinha et al. 2020), config.d_stats
 keeps logit statistics, among them the overfitting indicator r_t = E[sign D(real)] (Karras et al. 2020): all inside the loss
 launch (functional.AdvLossEx), nothing read back; `d_stats()` is the one call that synchronizes.
+`evaluate_samples(real, n_samples=N, embed=...)` measures generation from noise (n_cond = 0): the Frechet and the kernel distance
+between features of real and of generated clips (distmetrics.py; the statistic of FVD / FID / KID, on the device).  `embed` is the
+caller's feature extractor or "Dt" / "Ds", this Trainer's own discriminator features -- comparable only under ONE fixed
+discriminator snapshot.  It leaves no trace in the training state or in any random stream.
 Out of scope: tensorboard logging, GIF / MP4 files, dataset loaders.
 """
 import contextlib
@@ -1227,6 +1231,113 @@ class Trainer(object):
                     t.copy_(old)
         table = torch.stack([mse, ssim]).permute(0, 2, 1, 3).cpu().numpy()          # the one copy to the host
         return M.aggregate_prediction(table[0], table[1])
+
+    # ---- distribution distances of generated against real clips (no counterpart in the reference; distmetrics.py)
+    def _sample_embedder(self, embed):
+        """-> frames [B, T, 3, H, W] (raw [-1, 1], contiguous) -> features [B, d] fp32 on the device."""
+        from . import distmetrics as DM
+        if callable(embed):
+            return lambda frames: embed(frames.permute(0, 2, 1, 3, 4).contiguous())
+        if embed == "Dt":
+            extract = DM.DiscFeatures(self.D_t)
+            return lambda frames: extract(vid_downsample(frames))
+        if embed == "Ds":
+            extract, T, k = DM.DiscFeatures(self.D_s), self.n_frames, self.k_sample
+            ids = (torch.arange(k) * T) // k                          # k evenly spaced frames: no random draw in an evaluation
+            return lambda frames: extract(sample_k_frames(frames, T, k, ids))
+        raise ValueError(f"embed={embed!r}: \"Dt\", \"Ds\" or a callable clips [B, 3, T, H, W] -> features [B, d]")
+
+    @torch.no_grad()
+    def evaluate_samples(self, real, *, n_samples, embed="Dt", batch=None, use_ema=False, standing_stats=None, truncation=None,
+                         seed=0, real_stats=None, kid=True):
+        """Frechet and kernel distance between the features of real clips and of clips generated from noise (n_cond = 0): the
+        statistic of FVD / FID / KID (distmetrics.py).  real: a loader or any iterable of (clips [B, 3, T, H, W] in [-1, 1],
+        labels [B]); its first n_samples clips are used.  embed: a callable clips [B, 3, T, H, W] -> features [B, d] (fp32, on
+        the device; e.g. an I3D network with the published weights gives FVD), or "Dt" / "Ds": the pooled final activation of
+        this Trainer's own temporal / spatial discriminator (distmetrics.DiscFeatures; D_t on the downsampled clip, D_s on
+        k_sample evenly spaced frames), averaged over the clip.  A DISCRIMINATOR-FEATURE DISTANCE IS COMPARABLE ONLY UNDER ONE
+        FIXED DISCRIMINATOR SNAPSHOT: the live D moves with every training step, so compare generator checkpoints, averaged
+        against live weights or truncation values with the discriminator of ONE checkpoint loaded, never across training steps.
+        As many clips are generated as real ones were read, with the real clips' labels, z from a private generator seeded with
+        `seed` (truncation as in sample()), `batch` at a time (default: the first real batch's size), through the generator's
+        sampling path: eval mode, use_ema / standing_stats as in sample().  real_stats: FeatureStats of the real set computed
+        earlier (FeatureStats.load); the real clips are then embedded only when kid is on.
+        -> {"fd", "kid_mean", "kid_std" (None with kid=False), "n_real", "n_fake", "d"}; the KID subsets (100 of 1000 rows,
+        clipped to the sample count) are drawn from a private numpy generator seeded with `seed`.
+        Like rollout() and save_samples() the call leaves no trace: weights, spectral-norm u / v of all three networks, batch-norm
+        statistics and every random stream of the training run (torch's default generator included, which a shuffling loader
+        draws from when it is iterated) are bit-equal before and after."""
+        from . import distmetrics as DM
+        if self.n_cond:
+            raise RuntimeError("evaluate_samples() measures generation from noise (n_cond = 0); a frame-conditional Trainer has "
+                               "evaluate_prediction()")
+        n_samples = int(n_samples)
+        if n_samples < 2:
+            raise ValueError(f"n_samples={n_samples}: a covariance needs at least two clips")
+        embedder = self._sample_embedder(embed)
+        gen = torch.Generator().manual_seed(int(seed))
+        rng_state = torch.get_rng_state()
+        want_real = real_stats is None or kid
+        stats_r = stats_f = None
+        feats_r, feats_f, labels_all = [], [], []
+        n_real = 0
+        try:
+            for clips, labels in real:
+                take = min(clips.shape[0], n_samples - n_real)
+                if take <= 0:
+                    break
+                labels_all.append(self._check_labels(torch.as_tensor(labels)[:take].cpu()))
+                if batch is None:
+                    batch = clips.shape[0]
+                if want_real:
+                    frames = to_device_async(clips[:take], self.device).to(torch.float32).permute(0, 2, 1, 3, 4).contiguous()
+                    f = embedder(frames)
+                    if real_stats is None:
+                        if stats_r is None:
+                            stats_r = DM.FeatureStats(f.shape[1], self.device)
+                        stats_r.update(f)
+                    if kid:
+                        feats_r.append(f)
+                n_real += take
+                if n_real >= n_samples:
+                    break
+        finally:
+            torch.set_rng_state(rng_state)
+        if n_real < 2:
+            raise ValueError(f"`real` delivered {n_real} clips: at least two are needed")
+        labels_all = torch.cat(labels_all)
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f"batch={batch}")
+        with self._sampling_weights(use_ema, standing_stats):
+            frozen = self._g_frozen_tensors()
+            saved = [t.clone() for t in frozen]
+            self.G.eval()
+            try:
+                for lo in range(0, n_real, batch):
+                    y = labels_all[lo:lo + batch]
+                    z = (torch.randn(y.shape[0], self.z_dim, generator=gen) if truncation is None
+                         else truncated_z(y.shape[0], self.z_dim, truncation, generator=gen))
+                    fake = self.G(to_device_async(z, self.device), to_device_async(y, self.device))
+                    f = embedder(fake.to(torch.float32).contiguous())
+                    if stats_f is None:
+                        stats_f = DM.FeatureStats(f.shape[1], self.device)
+                    stats_f.update(f)
+                    if kid:
+                        feats_f.append(f)
+            finally:
+                self.G.train()
+                for t, old in zip(frozen, saved):
+                    t.copy_(old)
+        ref = real_stats if real_stats is not None else stats_r
+        if ref.d != stats_f.d:
+            raise ValueError(f"real statistics of width {ref.d} against generated features of width {stats_f.d}")
+        out = {"fd": DM.frechet_distance(ref, stats_f), "kid_mean": None, "kid_std": None, "n_real": n_real,
+               "n_fake": stats_f.n, "d": stats_f.d}
+        if kid:
+            res = DM.kid(torch.cat(feats_r), torch.cat(feats_f), seed=int(seed))
+            out["kid_mean"], out["kid_std"] = res["mean"], res["std"]
+        return out
 
     # ---- trainer.py:337-343 / 375-382: reference-compatible checkpoints
     def save_models(self, step):
