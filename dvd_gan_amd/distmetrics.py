@@ -10,7 +10,11 @@ taken under different discriminator weights are not comparable.
 
 Second moments and kernel sums run on the device (libdvdgan_hip_eval.so, fp32 MFMA with fp64 state, deterministic); only the
 final small tables cross to the host.  The last step of the Frechet distance, O(d^3) on two d x d matrices once per evaluation,
-is numpy fp64 on the host on purpose."""
+is numpy fp64 on the host on purpose.
+
+prdc() adds the k-nearest-neighbour manifold statistics -- improved precision / recall (Kynkaanniemi et al. 2019) and density /
+coverage (Naeem et al. 2020) -- which tell poor samples from too few kinds of samples; their pairwise distances run on
+libdvdgan_hip_prdc.so."""
 import numpy as np
 import torch
 
@@ -169,6 +173,47 @@ def kid(x, y, *, n_subsets=100, subset_size=1000, seed=0):
     values, _ = K.eval_kid(x, y, torch.from_numpy(ix), torch.from_numpy(iy))
     values = values.cpu().numpy()
     return {"mean": float(values.mean()), "std": float(values.std()), "values": values}
+
+
+def knn_radii(x, k, pivot=None):
+    """Squared distance of every row of x [n, d] (device fp32) to its k-th nearest OTHER row (by position: duplicate rows give zero
+    radii) -> device fp64 [n].  Distances are those of fl32(x - pivot): d2 = |a|^2 + |b|^2 - 2 a.b with fp64 norms and the dot
+    product on fp32 MFMA (dvd_prdc_knn_radii); pivot fp32 [d], None = zeros.  No host sync."""
+    return K.eval_knn_radii(x, k, pivot)
+
+
+def prdc(real, fake, k=5):
+    """Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of generated features
+    fake [m, d] against real features real [n, d] (device fp32), with B(x_i) the ball about x_i through its k-th nearest
+    neighbour WITHIN ITS OWN SET:
+      precision = share of fake rows inside some real ball          recall   = share of real rows inside some fake ball
+      density   = sum_j #{real balls holding fake_j} / (k m)        coverage = share of real rows whose ball holds a fake row
+    -> {"precision", "recall", "density", "coverage", "k", "n_real", "n_fake"}.  The paper of precision / recall uses k = 3, the
+    one of density / coverage k = 5.  All distances are taken about one pivot, the column mean of `real` (far from the origin the
+    fp32 dot products would otherwise cancel); radii and counts run on the device (libdvdgan_hip_prdc.so: fp32 MFMA products,
+    fp64 norms and comparisons, deterministic), one copy of the per-row tables crosses to the host, and the ratios are integers
+    and fp64 there.  A comparison d2 <= r2 is decided up to the rounding of the fp32 dot product (include/dvdgan_hip_prdc.h).
+    As for FeatureStats: with discriminator features ("Dt" / "Ds") the values compare ONLY under one fixed discriminator
+    snapshot."""
+    if real.dim() != 2 or fake.dim() != 2:
+        raise ValueError(f"feature sets must be [rows, d], got {tuple(real.shape)} / {tuple(fake.shape)}")
+    if real.shape[1] != fake.shape[1]:
+        raise ValueError(f"real {tuple(real.shape)} and fake {tuple(fake.shape)} differ in the feature width")
+    n, m, k = real.shape[0], fake.shape[0], int(k)
+    if k < 1 or k >= min(n, m):
+        raise ValueError(f"k={k} needs 1 <= k < min(n, m) = {min(n, m)}")
+    if k > L.PRDC_MAX_K:
+        raise ValueError(f"k={k} above {L.PRDC_MAX_K}")
+    pivot = K.eval_column_mean(real)
+    r2_real, r2_fake = K.eval_knn_radii(real, k, pivot), K.eval_knn_radii(fake, k, pivot)
+    cnt_fr, _ = K.eval_ball_count(fake, real, r2_real, pivot)                # per fake row: real balls that hold it
+    cnt_rf, dmin_rf = K.eval_ball_count(real, fake, r2_fake, pivot)          # per real row: fake balls that hold it; nearest fake row
+    table = torch.cat([cnt_fr.double(), cnt_rf.double(), dmin_rf, r2_real]).cpu().numpy()      # the one copy to the host
+    cnt_fr, cnt_rf = table[:m].astype(np.int64), table[m:m + n].astype(np.int64)
+    dmin_rf, r2_real = table[m + n:m + 2 * n], table[m + 2 * n:]
+    return {"precision": float(np.count_nonzero(cnt_fr > 0)) / m, "recall": float(np.count_nonzero(cnt_rf > 0)) / n,
+            "density": float(int(cnt_fr.sum())) / (k * m), "coverage": float(np.count_nonzero(dmin_rf <= r2_real)) / n,
+            "k": k, "n_real": n, "n_fake": m}
 
 
 class DiscFeatures:

@@ -727,3 +727,61 @@ def eval_kid(x, y, ix, iy):
                                   tab_d[0].data_ptr(), tab_d[1].data_ptr(), n_sub, s, L.ptr(ws), L.ptr(out), L.ptr(terms),
                                   L.stream()))
     return out, terms
+
+
+# ------------------------------------------------------------------ libdvdgan_hip_prdc.so: nearest-neighbour radii and ball counts
+def _prdc_pivot(pivot, d, device):
+    if pivot is None:
+        return None
+    if pivot.dtype != torch.float32 or pivot.numel() != d or pivot.device != device or not pivot.is_contiguous():
+        raise ValueError(f"pivot must be a contiguous device fp32 vector [{d}], got {tuple(pivot.shape)} {pivot.dtype} on {pivot.device}")
+    return pivot
+
+
+def _prdc_ws(n_doubles, device):
+    if n_doubles < 0:
+        L.prdc_check(int(n_doubles))
+    return torch.empty(int(n_doubles), dtype=torch.float64, device=device)
+
+
+def eval_column_mean(x):
+    """dvd_prdc_column_mean: x [n, d] (device fp32, row stride >= d) -> fp32 [d], the column mean as dvd_eval_moments_update's first
+    call computes it; no host sync."""
+    x, n, d, ld = _rows_f32(x, "features")
+    pivot = torch.empty(d, dtype=torch.float32, device=x.device)
+    L.prdc_check(L.prdc_lib().dvd_prdc_column_mean(x.data_ptr(), n, d, ld, L.ptr(pivot), L.stream()))
+    return pivot
+
+
+def eval_knn_radii(x, k, pivot=None):
+    """dvd_prdc_knn_radii: x [n, d] (device fp32, row stride >= d) -> fp64 [n] on the device, the squared distance of every row to
+    its k-th nearest other row (distances of fl32(x - pivot), pivot fp32 [d] or None = zeros); no host sync."""
+    x, n, d, ld = _rows_f32(x, "features")
+    pivot = _prdc_pivot(pivot, d, x.device)
+    lib = L.prdc_lib()
+    ws = _prdc_ws(lib.dvd_prdc_knn_ws_doubles(n, int(k)), x.device)
+    r2 = torch.empty(n, dtype=torch.float64, device=x.device)
+    L.prdc_check(lib.dvd_prdc_knn_radii(x.data_ptr(), n, d, ld, L.ptr(pivot), int(k), L.ptr(ws), L.ptr(r2), L.stream()))
+    return r2
+
+
+def eval_ball_count(q, r, r2=None, pivot=None):
+    """dvd_prdc_ball_count: q [nq, d], r [nr, d] (device fp32), r2 fp64 [nr] or None -> (count int32 [nq] or None, dmin fp64 [nq]):
+    in how many balls (centre r_i, squared radius r2_i) every row of q lies, and its squared distance to the nearest row of r;
+    no host sync."""
+    q, nq, d, ldq = _rows_f32(q, "q")
+    r, nr, d2, ldr = _rows_f32(r, "r")
+    if d != d2 or q.device != r.device:
+        raise ValueError(f"q {tuple(q.shape)} and r {tuple(r.shape)} must share the feature width and the device")
+    pivot = _prdc_pivot(pivot, d, q.device)
+    count = None
+    if r2 is not None:
+        if r2.dtype != torch.float64 or r2.shape != (nr,) or r2.device != q.device or not r2.is_contiguous():
+            raise ValueError(f"r2 must be a contiguous device fp64 vector [{nr}], got {tuple(r2.shape)} {r2.dtype} on {r2.device}")
+        count = torch.empty(nq, dtype=torch.int32, device=q.device)
+    lib = L.prdc_lib()
+    ws = _prdc_ws(lib.dvd_prdc_ball_ws_doubles(nq, nr), q.device)
+    dmin = torch.empty(nq, dtype=torch.float64, device=q.device)
+    L.prdc_check(lib.dvd_prdc_ball_count(q.data_ptr(), nq, ldq, r.data_ptr(), nr, ldr, d, L.ptr(pivot), L.ptr(r2), L.ptr(ws),
+                                         L.ptr(count), L.ptr(dmin), L.stream()))
+    return count, dmin

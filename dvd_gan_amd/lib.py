@@ -254,6 +254,47 @@ def eval_check(code):
         raise RuntimeError(f"libdvdgan_hip_eval: {eval_lib().dvd_eval_strerror(code).decode()} (code {code})")
 
 
+# ---- libdvdgan_hip_prdc.so (include/dvdgan_hip_prdc.h): k-nearest-neighbour radii and ball counts of sample features (precision /
+# recall / density / coverage, distmetrics.py), the fourth library with the same handshake (tests/test_prdc_cpu.py compares the
+# constants and the table with the header and the exports with the table)
+PRDC_MAX_D, PRDC_MAX_K, PRDC_TILE, PRDC_MAX_ROWS = 4096, 16, 64, 1 << 24
+PRDC_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
+                         if name.startswith("PRDC_") and isinstance(value, int)}
+PRDC_SIGNATURES = {
+    "dvd_prdc_strerror": "s i",
+    "dvd_prdc_column_mean": "i p lil p p",
+    "dvd_prdc_knn_ws_doubles": "l li",
+    "dvd_prdc_knn_radii": "i p lil p i pp p",
+    "dvd_prdc_ball_ws_doubles": "l ll",
+    "dvd_prdc_ball_count": "i pll pll i p p p pp p",
+}
+PRDC_LIB_PATH = os.environ.get("DVD_PRDC_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_prdc.so")
+_prdc_lib = None
+
+
+def prdc_lib():
+    """The loaded libdvdgan_hip_prdc.so, typed from PRDC_SIGNATURES.  Raises (never falls back) when it has not been built."""
+    global _prdc_lib
+    if _prdc_lib is None:
+        if not os.path.exists(PRDC_LIB_PATH):
+            raise RuntimeError(
+                f"{PRDC_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(dvd_gan_amd has no CPU / eager fallback)")
+        loaded = C.CDLL(PRDC_LIB_PATH)
+        for name, sig in PRDC_SIGNATURES.items():
+            fn = getattr(loaded, name, None)
+            if fn is None:
+                raise RuntimeError(f"libdvdgan_hip_prdc.so exports no {name} -- lib.py and include/dvdgan_hip_prdc.h disagree")
+            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
+        _prdc_lib = loaded
+    return _prdc_lib
+
+
+def prdc_check(code):
+    if code != 0:
+        raise RuntimeError(f"libdvdgan_hip_prdc: {prdc_lib().dvd_prdc_strerror(code).decode()} (code {code})")
+
+
 ABI_VERSION = 13
 
 

@@ -1249,7 +1249,7 @@ class Trainer(object):
 
     @torch.no_grad()
     def evaluate_samples(self, real, *, n_samples, embed="Dt", batch=None, use_ema=False, standing_stats=None, truncation=None,
-                         seed=0, real_stats=None, kid=True):
+                         seed=0, real_stats=None, kid=True, prdc_k=None):
         """Frechet and kernel distance between the features of real clips and of clips generated from noise (n_cond = 0): the
         statistic of FVD / FID / KID (distmetrics.py).  real: a loader or any iterable of (clips [B, 3, T, H, W] in [-1, 1],
         labels [B]); its first n_samples clips are used.  embed: a callable clips [B, 3, T, H, W] -> features [B, d] (fp32, on
@@ -1264,6 +1264,9 @@ class Trainer(object):
         earlier (FeatureStats.load); the real clips are then embedded only when kid is on.
         -> {"fd", "kid_mean", "kid_std" (None with kid=False), "n_real", "n_fake", "d"}; the KID subsets (100 of 1000 rows,
         clipped to the sample count) are drawn from a private numpy generator seeded with `seed`.
+        prdc_k: an int k adds "precision", "recall", "density", "coverage" and "prdc_k" (distmetrics.prdc on the kept features
+        of both sets: k = 3 is the precision / recall paper's, k = 5 the density / coverage paper's; the real clips are then
+        embedded even when real_stats are given); None (the default) computes, launches and returns exactly what it did without.
         Like rollout() and save_samples() the call leaves no trace: weights, spectral-norm u / v of all three networks, batch-norm
         statistics and every random stream of the training run (torch's default generator included, which a shuffling loader
         draws from when it is iterated) are bit-equal before and after."""
@@ -1277,7 +1280,10 @@ class Trainer(object):
         embedder = self._sample_embedder(embed)
         gen = torch.Generator().manual_seed(int(seed))
         rng_state = torch.get_rng_state()
-        want_real = real_stats is None or kid
+        if prdc_k is not None and int(prdc_k) < 1:
+            raise ValueError(f"prdc_k={prdc_k}")
+        keep = kid or prdc_k is not None
+        want_real = real_stats is None or keep
         stats_r = stats_f = None
         feats_r, feats_f, labels_all = [], [], []
         n_real = 0
@@ -1296,7 +1302,7 @@ class Trainer(object):
                         if stats_r is None:
                             stats_r = DM.FeatureStats(f.shape[1], self.device)
                         stats_r.update(f)
-                    if kid:
+                    if keep:
                         feats_r.append(f)
                 n_real += take
                 if n_real >= n_samples:
@@ -1323,7 +1329,7 @@ class Trainer(object):
                     if stats_f is None:
                         stats_f = DM.FeatureStats(f.shape[1], self.device)
                     stats_f.update(f)
-                    if kid:
+                    if keep:
                         feats_f.append(f)
             finally:
                 self.G.train()
@@ -1337,6 +1343,9 @@ class Trainer(object):
         if kid:
             res = DM.kid(torch.cat(feats_r), torch.cat(feats_f), seed=int(seed))
             out["kid_mean"], out["kid_std"] = res["mean"], res["std"]
+        if prdc_k is not None:
+            res = DM.prdc(torch.cat(feats_r), torch.cat(feats_f), k=int(prdc_k))
+            out.update({key: res[key] for key in ("precision", "recall", "density", "coverage")}, prdc_k=res["k"])
         return out
 
     # ---- trainer.py:337-343 / 375-382: reference-compatible checkpoints
