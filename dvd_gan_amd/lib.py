@@ -295,6 +295,50 @@ def prdc_check(code):
         raise RuntimeError(f"libdvdgan_hip_prdc: {prdc_lib().dvd_prdc_strerror(code).decode()} (code {code})")
 
 
+# ---- libdvdgan_hip_aug.so (include/dvdgan_hip_aug.h): clip-consistent augmentation of the discriminators' inputs and its
+# transpose (augment.py), the fifth library with the same handshake (tests/test_aug_cpu.py compares the constants and the table
+# with the header and the exports with the table)
+AUG_ABI_VERSION = 1
+AUG_COLS = 9
+(AUG_B, AUG_S, AUG_C, AUG_DX, AUG_DY, AUG_CY0, AUG_CX0, AUG_CH, AUG_CW) = range(AUG_COLS)
+AUG_MAX_SIDE, AUG_THREADS, AUG_MAX_FRAMES = 4096, 256, (1 << 24) - 1
+AUG_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
+                        if name.startswith("AUG_") and isinstance(value, int)}
+AUG_SIGNATURES = {
+    "dvd_aug_abi_version": "i",
+    "dvd_aug_strerror": "s i",
+    "dvd_aug_clip_forward": "i ppp liii p",
+    "dvd_aug_clip_backward": "i ppp liii p",
+}
+AUG_LIB_PATH = os.environ.get("DVD_AUG_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_aug.so")
+_aug_lib = None
+
+
+def aug_lib():
+    """The loaded libdvdgan_hip_aug.so, typed from AUG_SIGNATURES.  Raises (never falls back) when it has not been built."""
+    global _aug_lib
+    if _aug_lib is None:
+        if not os.path.exists(AUG_LIB_PATH):
+            raise RuntimeError(
+                f"{AUG_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(dvd_gan_amd has no CPU / eager fallback)")
+        loaded = C.CDLL(AUG_LIB_PATH)
+        for name, sig in AUG_SIGNATURES.items():
+            fn = getattr(loaded, name, None)
+            if fn is None:
+                raise RuntimeError(f"libdvdgan_hip_aug.so exports no {name} -- lib.py and include/dvdgan_hip_aug.h disagree")
+            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
+        if loaded.dvd_aug_abi_version() != AUG_ABI_VERSION:
+            raise RuntimeError("libdvdgan_hip_aug.so ABI version mismatch: rebuild it")
+        _aug_lib = loaded
+    return _aug_lib
+
+
+def aug_check(code):
+    if code != 0:
+        raise RuntimeError(f"libdvdgan_hip_aug: {aug_lib().dvd_aug_strerror(code).decode()} (code {code})")
+
+
 ABI_VERSION = 13
 
 

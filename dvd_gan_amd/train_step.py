@@ -37,6 +37,10 @@ config.lecam = lambda > 0 adds LeCam regularization (Tseng et al. 2021) to the d
 lets the generator step take gradient only from the samples each discriminator scores highest (Sinha et al. 2020), config.d_stats
 keeps logit statistics, among them the overfitting indicator r_t = E[sign D(real)] (Karras et al. 2020): all inside the loss
 launch (functional.AdvLossEx), nothing read back; `d_stats()` is the one call that synchronizes.
+config.d_aug = "color,translation,cutout" (any subset) transforms what the discriminators see, real and generated clips alike and
+every frame of a clip alike (augment.py: Zhao et al. 2020, two HIP launches, the generator's gradient passes through the
+transform); each group applies to a clip with probability config.d_aug_p, which config.d_aug_target > 0 steers by r_t every
+config.d_aug_interval steps (Karras et al. 2020; `d_aug_p` is the current value).
 `evaluate_samples(real, n_samples=N, embed=...)` measures generation from noise (n_cond = 0): the Frechet and the kernel distance
 between features of real and of generated clips (distmetrics.py; the statistic of FVD / FID / KID, on the device).  `embed` is the
 caller's feature extractor or "Dt" / "Ds", this Trainer's own discriminator features -- comparable only under ONE fixed
@@ -53,6 +57,7 @@ from . import functional as Fn
 from . import kern as K
 from . import lib as L
 from . import dist as D
+from .augment import ClipAugment, ada_update, draw_params, parse_policy
 from .dist import GradExchange
 from .disc_nets import SpatialDiscriminator, TemporalDiscriminator
 from .gen_net import Generator
@@ -208,7 +213,24 @@ class Trainer(object):
             raise ValueError(f"lecam={self.lecam} (finite, >= 0), lecam_decay={self.lecam_decay} (in [0, 1)), "
                              f"lecam_start={self.lecam_start} (>= 0), g_topk={self.g_topk} (in [0, 1]), "
                              f"g_topk_decay={self.g_topk_decay} (in (0, 1])")
-        self._adv_ex = self.lecam > 0.0 or self.g_topk > 0.0 or self._d_stats_on
+        # augmentation of what the discriminators see (d_aug = "" = off: no table, no generator, no launch): the groups of
+        # augment.POLICIES, the probability a group applies to a clip with, the r_t it is steered towards (0 = fixed p), steps
+        # between two adjustments, thousands of real clips in which p crosses [0, 1], seed of the tables' private generator
+        self.d_aug = parse_policy(getattr(c, "d_aug", "") or "")
+        self.d_aug_p = float(getattr(c, "d_aug_p", 1.0))          # the current p: adaptive runs move it (d_aug_target > 0)
+        self.d_aug_target = float(getattr(c, "d_aug_target", 0.0))
+        self.d_aug_interval = int(getattr(c, "d_aug_interval", 4))
+        self.d_aug_kimg = float(getattr(c, "d_aug_kimg", 500))
+        self.d_aug_seed = int(getattr(c, "d_aug_seed", 0))
+        if (not 0.0 <= self.d_aug_p <= 1.0 or not 0.0 <= self.d_aug_target < 1.0 or self.d_aug_interval < 1
+                or not 0.0 < self.d_aug_kimg < float("inf")):
+            raise ValueError(f"d_aug_p={self.d_aug_p} (in [0, 1]), d_aug_target={self.d_aug_target} (in [0, 1), 0 = fixed p), "
+                             f"d_aug_interval={self.d_aug_interval} (>= 1), d_aug_kimg={self.d_aug_kimg} (finite, > 0)")
+        self._aug_adaptive = bool(self.d_aug) and self.d_aug_target > 0.0
+        self._aug_gen = None          # the tables' generator, made below once the rank is known
+        self._aug_steps = 0           # steps taken with d_aug on
+        self._aug_adjustments = 0     # adjustments of p made
+        self._adv_ex = self.lecam > 0.0 or self.g_topk > 0.0 or self._d_stats_on or self._aug_adaptive
         self._anchors = None          # fp32 [2 slots][D_s, D_t][real, fake] on the device, when lecam > 0
         self._adv_stats = None        # fp32 [6][lib.ADV_NSTAT]: D_s real / fake, D_t real / fake, G step D_s / D_t
         self._lecam_it = 0            # D iterations done
@@ -268,6 +290,11 @@ class Trainer(object):
             if not self.exchange.active and os.environ.get("DVD_D_REAL_EARLY", "0") == "1":
                 self._aux = torch.cuda.Stream()
         self.rank = torch.distributed.get_rank() if self.exchange.active else 0
+        if self.d_aug:
+            if self._aug_adaptive and self.exchange.active:
+                raise ValueError(f"d_aug_target={self.d_aug_target}: an adaptive augmentation probability is not served in a "
+                                 "data-parallel run (every rank would have to agree on p); use a fixed d_aug_p")
+            self._aug_gen = self._new_aug_gen()
         self.build_model()
         if self.pretrained_model:
             self.load_pretrained_model()
@@ -287,6 +314,33 @@ class Trainer(object):
             if base is None:
                 base = int(torch.randint(0, 2 ** 31 - 1, (1,)))
             self.noise_gen = torch.Generator().manual_seed((int(base) * 1000003 + 7919 * self.rank + 1) % (2 ** 63 - 1))
+
+    def _new_aug_gen(self):
+        """The private generator of the augmentation tables: d_aug_seed, mixed with the rank in a data-parallel run as noise_gen's
+        seed is.  Neither the default generator nor noise_gen is touched by a table."""
+        seed = self.d_aug_seed
+        if self.exchange.active:
+            seed = (int(seed) * 1000003 + 7919 * self.rank + 1) % (2 ** 63 - 1)
+        return torch.Generator().manual_seed(seed)
+
+    def _aug_table(self, draws, key, B, H, W):
+        """One parameter table [B, lib.AUG_COLS] on the device: draws[key] (test aid) or a draw from the private generator."""
+        if draws is not None and key in draws:
+            tab = torch.as_tensor(draws[key], dtype=torch.float32).reshape(B, L.AUG_COLS).contiguous()
+        else:
+            tab = draw_params(B, H, W, self.d_aug, self.d_aug_p, self._aug_gen)
+        return to_device_async(tab, self.device)
+
+    def _aug_adapt(self):
+        """After every d_aug_interval-th step: p follows the sign of r_t - d_aug_target, r_t the mean of the two discriminators'
+        E[sign D(real)] of this step (one synchronizing read of two floats)."""
+        self._aug_steps += 1
+        if not self._aug_adaptive or self._aug_steps % self.d_aug_interval:
+            return
+        r = self._adv_stats[:, L.ADV_STAT_SIGN].cpu().tolist()
+        self.d_aug_p = ada_update(self.d_aug_p, 0.5 * (r[0] + r[2]), self.d_aug_target, self.batch_size, self.d_aug_interval,
+                                  self.d_aug_kimg)
+        self._aug_adjustments += 1
 
     # ---- trainer.py:345-366
     def build_model(self):
@@ -499,16 +553,27 @@ class Trainer(object):
         ex = self.exchange
         fg = self.frame_gen
         draws_all = draws
+        aug = bool(getattr(self, "d_aug", ()))
         for _ in range(self.d_iters):
             if isinstance(draws_all, (list, tuple)):              # test aid: one dict of draws per discriminator iteration
                 draws = draws_all[_]
             ids_real = draw_frame_ids(T, k, fg) if draws is None else torch.as_tensor(draws["perm_real"])[:k].sort()[0]
-            real_s = sample_k_frames(real_videos, T + Kc, k, ids_real + Kc if Kc else ids_real)
+            early = self._aux is not None
+            real_in = real_videos
+            if aug:
+                # one table for the real clips and an independent one for the fake clips; both discriminators see the same
+                # transform of a clip (the frame gather and the 2 x 2 average work on the augmented clip)
+                tab_real = self._aug_table(draws, "aug_real", real_videos.shape[0], *real_videos.shape[-2:])
+                tab_fake = self._aug_table(draws, "aug_fake", self.batch_size if draws is None else len(draws["z"]),
+                                           *real_videos.shape[-2:])
+                if not early:
+                    real_in = ClipAugment.apply(real_videos, tab_real)
+            if not (aug and early):
+                real_s = sample_k_frames(real_in, T + Kc, k, ids_real + Kc if Kc else ids_real)
             z = to_device_async(torch.randn(self.batch_size, self.z_dim, generator=self.noise_gen) if draws is None
                                 else torch.as_tensor(draws["z"]), self.device)
             z_class = self.label_sample() if draws is None else to_device_async(self._check_labels(torch.as_tensor(draws["z_class"])), self.device)
             ex.finish("G")
-            early = self._aux is not None
             if early:
                 # The discriminator passes over the REAL clips need nothing from the generator: they run on a second stream beside
                 # the 4 x 4 / 8 x 8 time loops at the start of the generator forward, the one phase of the step with idle CUs and
@@ -517,14 +582,27 @@ class Trainer(object):
                 cur = torch.cuda.current_stream()
                 self._aux.wait_stream(cur)
                 with torch.cuda.stream(self._aux):
+                    if aug:
+                        # (real_in / real_s are allocated on this stream, like real_d: the weight-gradient launches that read
+                        #  them on the side stream are fenced by Fn.join_side() before the step ends, and the next step's
+                        #  wait_stream orders this stream behind the chain before any block can be reused)
+                        real_in = ClipAugment.apply(real_videos, tab_real)
+                        real_s = sample_k_frames(real_in, T + Kc, k, ids_real + Kc if Kc else ids_real)
                     ds_loss_real = self._site_loss(self.D_s(real_s, real_labels), True, 0)
-                    real_d = vid_downsample(real_videos)
+                    real_d = vid_downsample(real_in)
                     dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
-                for t_ in (real_s, real_videos, real_labels):
+                for t_ in (real_videos, real_labels) + ((tab_real,) if aug else (real_s,)):
                     t_.record_stream(self._aux)
             fake_videos = self.G(z, z_class, hidden, cond=cond)
             ids_fake = draw_frame_ids(T, k, fg) if draws is None else torch.as_tensor(draws["perm_fake"])[:k].sort()[0]
-            fake_s = sample_k_frames(fake_videos, T, k, ids_fake)
+            fake_in, cond_in = fake_videos, cond
+            if aug:
+                # the generator step reuses fake_s / fake_d, so its gradient passes through the transform (autograd sums the two
+                # discriminators' gradients before the one backward launch); the context frames take the FAKE clips' rows
+                fake_in = ClipAugment.apply(fake_videos, tab_fake)
+                if cond is not None:
+                    cond_in = ClipAugment.apply(cond, tab_fake)
+            fake_s = sample_k_frames(fake_in, T, k, ids_fake)
             # ---------------- D_s
             if early:
                 cur.wait_stream(self._aux)
@@ -538,9 +616,9 @@ class Trainer(object):
             Fn.join_side()
             ex.start("Ds", self.ds_optimizer.grad)
             # ---------------- D_t (its forward/backward overlaps the D_s gradient exchange)
-            fake_d = vid_downsample(fake_videos) if cond is None else vid_downsample_cat(cond, fake_videos)
+            fake_d = vid_downsample(fake_in) if cond is None else vid_downsample_cat(cond_in, fake_in)
             if not early:
-                real_d = vid_downsample(real_videos)
+                real_d = vid_downsample(real_in)
                 dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
             dt_loss_fake = self._site_loss(self.D_t(fake_d.detach(), z_class), False, 3)
             ex.finish("Ds")
@@ -586,6 +664,8 @@ class Trainer(object):
         ex.finish("G")
         self.g_optimizer.step()
         self.g_lr_scher.step((g_s_loss + g_t_loss) if self._plateau else None)
+        if aug:
+            self._aug_adapt()
         return ds_loss_real, ds_loss_fake, dt_loss_real, dt_loss_fake, g_s_loss, g_t_loss
 
     # ---- trainer.py:189-343 (loop; logging reduced to a print)
@@ -644,6 +724,8 @@ class Trainer(object):
                     for tag in ("Ds", "Dt") if rep else ():
                         line += ", %s r_t: %.3f lecam: %.3e/%.3e" % (tag, rep[tag]["r_t"], rep[tag]["lecam_real"],
                                                                      rep[tag]["lecam_fake"])
+                    if getattr(self, "d_aug", ()):
+                        line += ", d_aug p: %.4f" % self.d_aug_p
                     print(line)
                 if sample_step and step % sample_step == 0:
                     self.save_samples(step)
@@ -691,7 +773,12 @@ class Trainer(object):
         from it."""
         from .checkpoint import host_rng_state
         loader = self.data_loader.state_dict() if hasattr(self.data_loader, "state_dict") else None
-        return {"rng": host_rng_state((("noise_gen", self.noise_gen),)), "loader": loader}
+        out = {"rng": host_rng_state((("noise_gen", self.noise_gen),)), "loader": loader}
+        if getattr(self, "d_aug", ()):
+            # the augmentation's own state: the current p, the tables' generator, steps and adjustments made so far
+            out["aug"] = {"p": float(self.d_aug_p), "generator": self._aug_gen.get_state().clone(),
+                          "steps": int(self._aug_steps), "adjustments": int(self._aug_adjustments)}
+        return out
 
     def save_state(self, step, wait=False):
         """Write everything step `step` leaves for step + 1 as `{step}_state.pt` under config.model_save_path/version: the
@@ -720,6 +807,8 @@ class Trainer(object):
                 return
         host = {"step": step, "epoch": int(getattr(self, "_epoch", 0)), "opt": {}, "sched": {}, "rng": own["rng"],
                 "loader": own["loader"], "frame_gen": None if self.frame_gen is None else self.frame_gen.get_state().clone()}
+        if "aug" in own:
+            host["aug"] = own["aug"]
         items, slabs = [], {}
         copy_of = lambda t: (lambda dst: dst.copy_(t))
         for tag, net in self._nets():
@@ -809,6 +898,18 @@ class Trainer(object):
                 for net, t in enumerate(saved):
                     self._anchors[:, net].copy_(t)
                 self._lecam_it = int(host["lecam_it"])
+        if getattr(self, "d_aug", ()):
+            saved = own.get("aug")
+            if saved is None:                   # the LeCam anchors' rule: the constructor's p, a fresh generator, and a note
+                self.d_aug_p = float(getattr(self.config, "d_aug_p", 1.0))
+                self._aug_gen = self._new_aug_gen()
+                self._aug_steps = self._aug_adjustments = 0
+                notes.append("d_aug: the state holds no augmentation state (it was written with d_aug off): p and the tables' "
+                             "generator start afresh")
+            else:
+                self.d_aug_p = float(saved["p"])
+                self._aug_gen.set_state(saved["generator"])
+                self._aug_steps, self._aug_adjustments = int(saved["steps"]), int(saved["adjustments"])
         self._epoch, self._resumed_step = int(host["epoch"]), step
         self._loader_resumed = own.get("loader") is not None and hasattr(self.data_loader, "load_state_dict")
         if self._loader_resumed:
