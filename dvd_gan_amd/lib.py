@@ -339,6 +339,50 @@ def aug_check(code):
         raise RuntimeError(f"libdvdgan_hip_aug: {aug_lib().dvd_aug_strerror(code).decode()} (code {code})")
 
 
+# ---- libdvdgan_hip_geom.so (include/dvdgan_hip_geom.h): the clip-consistent affine warp of the discriminators' inputs and its
+# transpose (geom_augment.py), the sixth library with the same handshake (tests/test_geom_cpu.py compares the constants and the
+# table with the header and the exports with the table)
+GEOM_ABI_VERSION = 1
+GEOM_COLS = 6
+(GEOM_A00, GEOM_A01, GEOM_A02, GEOM_A10, GEOM_A11, GEOM_A12) = range(GEOM_COLS)
+GEOM_MAX_SIDE, GEOM_THREADS, GEOM_MAX_FRAMES = 4096, 256, (1 << 24) - 1
+GEOM_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
+                         if name.startswith("GEOM_") and isinstance(value, int)}
+GEOM_SIGNATURES = {
+    "dvd_geom_abi_version": "i",
+    "dvd_geom_strerror": "s i",
+    "dvd_geom_clip_forward": "i ppp liii p",
+    "dvd_geom_clip_backward": "i ppp liii p",
+}
+GEOM_LIB_PATH = os.environ.get("DVD_GEOM_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_geom.so")
+_geom_lib = None
+
+
+def geom_lib():
+    """The loaded libdvdgan_hip_geom.so, typed from GEOM_SIGNATURES.  Raises (never falls back) when it has not been built."""
+    global _geom_lib
+    if _geom_lib is None:
+        if not os.path.exists(GEOM_LIB_PATH):
+            raise RuntimeError(
+                f"{GEOM_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(dvd_gan_amd has no CPU / eager fallback)")
+        loaded = C.CDLL(GEOM_LIB_PATH)
+        for name, sig in GEOM_SIGNATURES.items():
+            fn = getattr(loaded, name, None)
+            if fn is None:
+                raise RuntimeError(f"libdvdgan_hip_geom.so exports no {name} -- lib.py and include/dvdgan_hip_geom.h disagree")
+            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
+        if loaded.dvd_geom_abi_version() != GEOM_ABI_VERSION:
+            raise RuntimeError("libdvdgan_hip_geom.so ABI version mismatch: rebuild it")
+        _geom_lib = loaded
+    return _geom_lib
+
+
+def geom_check(code):
+    if code != 0:
+        raise RuntimeError(f"libdvdgan_hip_geom: {geom_lib().dvd_geom_strerror(code).decode()} (code {code})")
+
+
 ABI_VERSION = 13
 
 

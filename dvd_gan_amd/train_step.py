@@ -41,6 +41,9 @@ config.d_aug = "color,translation,cutout" (any subset) transforms what the discr
 every frame of a clip alike (augment.py: Zhao et al. 2020, two HIP launches, the generator's gradient passes through the
 transform); each group applies to a clip with probability config.d_aug_p, which config.d_aug_target > 0 steers by r_t every
 config.d_aug_interval steps (Karras et al. 2020; `d_aug_p` is the current value).
+config.d_aug_geom = "xflip,rot90,scale,rotate,aniso" (any subset) warps the clips before that: ADA's geometric group as one
+affine map per clip, bilinear with zero fill (geom_augment.py: two more HIP launches, the warp and its exact transpose, no
+atomics); it shares d_aug_p and its steering, d_aug_seed and the tables' generator with d_aug, and either works without the other.
 `evaluate_samples(real, n_samples=N, embed=...)` measures generation from noise (n_cond = 0): the Frechet and the kernel distance
 between features of real and of generated clips (distmetrics.py; the statistic of FVD / FID / KID, on the device).  `embed` is the
 caller's feature extractor or "Dt" / "Ds", this Trainer's own discriminator features -- comparable only under ONE fixed
@@ -58,6 +61,7 @@ from . import kern as K
 from . import lib as L
 from . import dist as D
 from .augment import ClipAugment, ada_update, draw_params, parse_policy
+from .geom_augment import ClipWarp, draw_geom, parse_geom
 from .dist import GradExchange
 from .disc_nets import SpatialDiscriminator, TemporalDiscriminator
 from .gen_net import Generator
@@ -217,6 +221,8 @@ class Trainer(object):
         # augment.POLICIES, the probability a group applies to a clip with, the r_t it is steered towards (0 = fixed p), steps
         # between two adjustments, thousands of real clips in which p crosses [0, 1], seed of the tables' private generator
         self.d_aug = parse_policy(getattr(c, "d_aug", "") or "")
+        # ... and the geometric groups of geom_augment.GEOM_POLICIES, applied before them; every other setting is shared
+        self.d_aug_geom = parse_geom(getattr(c, "d_aug_geom", "") or "")
         self.d_aug_p = float(getattr(c, "d_aug_p", 1.0))          # the current p: adaptive runs move it (d_aug_target > 0)
         self.d_aug_target = float(getattr(c, "d_aug_target", 0.0))
         self.d_aug_interval = int(getattr(c, "d_aug_interval", 4))
@@ -226,9 +232,9 @@ class Trainer(object):
                 or not 0.0 < self.d_aug_kimg < float("inf")):
             raise ValueError(f"d_aug_p={self.d_aug_p} (in [0, 1]), d_aug_target={self.d_aug_target} (in [0, 1), 0 = fixed p), "
                              f"d_aug_interval={self.d_aug_interval} (>= 1), d_aug_kimg={self.d_aug_kimg} (finite, > 0)")
-        self._aug_adaptive = bool(self.d_aug) and self.d_aug_target > 0.0
+        self._aug_adaptive = bool(self.d_aug or self.d_aug_geom) and self.d_aug_target > 0.0
         self._aug_gen = None          # the tables' generator, made below once the rank is known
-        self._aug_steps = 0           # steps taken with d_aug on
+        self._aug_steps = 0           # steps taken with d_aug or d_aug_geom on
         self._aug_adjustments = 0     # adjustments of p made
         self._adv_ex = self.lecam > 0.0 or self.g_topk > 0.0 or self._d_stats_on or self._aug_adaptive
         self._anchors = None          # fp32 [2 slots][D_s, D_t][real, fake] on the device, when lecam > 0
@@ -290,7 +296,7 @@ class Trainer(object):
             if not self.exchange.active and os.environ.get("DVD_D_REAL_EARLY", "0") == "1":
                 self._aux = torch.cuda.Stream()
         self.rank = torch.distributed.get_rank() if self.exchange.active else 0
-        if self.d_aug:
+        if self.d_aug or self.d_aug_geom:
             if self._aug_adaptive and self.exchange.active:
                 raise ValueError(f"d_aug_target={self.d_aug_target}: an adaptive augmentation probability is not served in a "
                                  "data-parallel run (every rank would have to agree on p); use a fixed d_aug_p")
@@ -330,6 +336,24 @@ class Trainer(object):
         else:
             tab = draw_params(B, H, W, self.d_aug, self.d_aug_p, self._aug_gen)
         return to_device_async(tab, self.device)
+
+    def _geom_table(self, draws, key, B, H, W):
+        """One table of warps [B, lib.GEOM_COLS] on the device: draws[key] (test aid) or a draw from the private generator."""
+        if draws is not None and key in draws:
+            tab = torch.as_tensor(draws[key], dtype=torch.float32).reshape(B, L.GEOM_COLS).contiguous()
+        else:
+            tab = draw_geom(B, H, W, self.d_aug_geom, self.d_aug_p, self._aug_gen)
+        return to_device_async(tab, self.device)
+
+    @staticmethod
+    def _d_view(clips, mats, tab):
+        """What the discriminators are given of `clips` [B, T, 3, H, W]: the warp first, then colour / translation / cutout
+        (Karras et al. 2020's order); a table that is None is a stage that is off."""
+        if mats is not None:
+            clips = ClipWarp.apply(clips, mats)
+        if tab is not None:
+            clips = ClipAugment.apply(clips, tab)
+        return clips
 
     def _aug_adapt(self):
         """After every d_aug_interval-th step: p follows the sign of r_t - d_aug_target, r_t the mean of the two discriminators'
@@ -553,7 +577,8 @@ class Trainer(object):
         ex = self.exchange
         fg = self.frame_gen
         draws_all = draws
-        aug = bool(getattr(self, "d_aug", ()))
+        aug, geo = bool(getattr(self, "d_aug", ())), bool(getattr(self, "d_aug_geom", ()))
+        tab_real = tab_fake = mat_real = mat_fake = None
         for _ in range(self.d_iters):
             if isinstance(draws_all, (list, tuple)):              # test aid: one dict of draws per discriminator iteration
                 draws = draws_all[_]
@@ -566,9 +591,14 @@ class Trainer(object):
                 tab_real = self._aug_table(draws, "aug_real", real_videos.shape[0], *real_videos.shape[-2:])
                 tab_fake = self._aug_table(draws, "aug_fake", self.batch_size if draws is None else len(draws["z"]),
                                            *real_videos.shape[-2:])
-                if not early:
-                    real_in = ClipAugment.apply(real_videos, tab_real)
-            if not (aug and early):
+            if geo:
+                # the warps' tables come after those: a run without d_aug_geom draws what it drew before
+                mat_real = self._geom_table(draws, "geom_real", real_videos.shape[0], *real_videos.shape[-2:])
+                mat_fake = self._geom_table(draws, "geom_fake", self.batch_size if draws is None else len(draws["z"]),
+                                            *real_videos.shape[-2:])
+            if (aug or geo) and not early:
+                real_in = self._d_view(real_videos, mat_real, tab_real)
+            if not ((aug or geo) and early):
                 real_s = sample_k_frames(real_in, T + Kc, k, ids_real + Kc if Kc else ids_real)
             z = to_device_async(torch.randn(self.batch_size, self.z_dim, generator=self.noise_gen) if draws is None
                                 else torch.as_tensor(draws["z"]), self.device)
@@ -582,26 +612,27 @@ class Trainer(object):
                 cur = torch.cuda.current_stream()
                 self._aux.wait_stream(cur)
                 with torch.cuda.stream(self._aux):
-                    if aug:
+                    if aug or geo:
                         # (real_in / real_s are allocated on this stream, like real_d: the weight-gradient launches that read
                         #  them on the side stream are fenced by Fn.join_side() before the step ends, and the next step's
                         #  wait_stream orders this stream behind the chain before any block can be reused)
-                        real_in = ClipAugment.apply(real_videos, tab_real)
+                        real_in = self._d_view(real_videos, mat_real, tab_real)
                         real_s = sample_k_frames(real_in, T + Kc, k, ids_real + Kc if Kc else ids_real)
                     ds_loss_real = self._site_loss(self.D_s(real_s, real_labels), True, 0)
                     real_d = vid_downsample(real_in)
                     dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
-                for t_ in (real_videos, real_labels) + ((tab_real,) if aug else (real_s,)):
+                for t_ in (real_videos, real_labels) + (tuple(t for t in (tab_real, mat_real) if t is not None) or (real_s,)):
                     t_.record_stream(self._aux)
             fake_videos = self.G(z, z_class, hidden, cond=cond)
             ids_fake = draw_frame_ids(T, k, fg) if draws is None else torch.as_tensor(draws["perm_fake"])[:k].sort()[0]
             fake_in, cond_in = fake_videos, cond
-            if aug:
+            if aug or geo:
                 # the generator step reuses fake_s / fake_d, so its gradient passes through the transform (autograd sums the two
-                # discriminators' gradients before the one backward launch); the context frames take the FAKE clips' rows
-                fake_in = ClipAugment.apply(fake_videos, tab_fake)
+                # discriminators' gradients before the one backward launch of each stage); the context frames take the FAKE
+                # clips' rows
+                fake_in = self._d_view(fake_videos, mat_fake, tab_fake)
                 if cond is not None:
-                    cond_in = ClipAugment.apply(cond, tab_fake)
+                    cond_in = self._d_view(cond, mat_fake, tab_fake)
             fake_s = sample_k_frames(fake_in, T, k, ids_fake)
             # ---------------- D_s
             if early:
@@ -664,7 +695,7 @@ class Trainer(object):
         ex.finish("G")
         self.g_optimizer.step()
         self.g_lr_scher.step((g_s_loss + g_t_loss) if self._plateau else None)
-        if aug:
+        if aug or geo:
             self._aug_adapt()
         return ds_loss_real, ds_loss_fake, dt_loss_real, dt_loss_fake, g_s_loss, g_t_loss
 
@@ -724,7 +755,7 @@ class Trainer(object):
                     for tag in ("Ds", "Dt") if rep else ():
                         line += ", %s r_t: %.3f lecam: %.3e/%.3e" % (tag, rep[tag]["r_t"], rep[tag]["lecam_real"],
                                                                      rep[tag]["lecam_fake"])
-                    if getattr(self, "d_aug", ()):
+                    if getattr(self, "d_aug", ()) or getattr(self, "d_aug_geom", ()):
                         line += ", d_aug p: %.4f" % self.d_aug_p
                     print(line)
                 if sample_step and step % sample_step == 0:
@@ -774,7 +805,7 @@ class Trainer(object):
         from .checkpoint import host_rng_state
         loader = self.data_loader.state_dict() if hasattr(self.data_loader, "state_dict") else None
         out = {"rng": host_rng_state((("noise_gen", self.noise_gen),)), "loader": loader}
-        if getattr(self, "d_aug", ()):
+        if getattr(self, "d_aug", ()) or getattr(self, "d_aug_geom", ()):
             # the augmentation's own state: the current p, the tables' generator, steps and adjustments made so far
             out["aug"] = {"p": float(self.d_aug_p), "generator": self._aug_gen.get_state().clone(),
                           "steps": int(self._aug_steps), "adjustments": int(self._aug_adjustments)}
@@ -898,7 +929,7 @@ class Trainer(object):
                 for net, t in enumerate(saved):
                     self._anchors[:, net].copy_(t)
                 self._lecam_it = int(host["lecam_it"])
-        if getattr(self, "d_aug", ()):
+        if getattr(self, "d_aug", ()) or getattr(self, "d_aug_geom", ()):
             saved = own.get("aug")
             if saved is None:                   # the LeCam anchors' rule: the constructor's p, a fresh generator, and a note
                 self.d_aug_p = float(getattr(self.config, "d_aug_p", 1.0))
