@@ -1,5 +1,5 @@
 #!/bin/bash
-# Builds libdvdgan_hip.so, libdvdgan_hip_adv.so, libdvdgan_hip_eval.so, libdvdgan_hip_prdc.so, libdvdgan_hip_aug.so and libdvdgan_hip_geom.so for gfx950 (cross-compiles without a GPU).  Usage: build.sh [-j N]
+# Builds libdvdgan_hip.so, libdvdgan_hip_adv.so, libdvdgan_hip_eval.so, libdvdgan_hip_prdc.so, libdvdgan_hip_aug.so, libdvdgan_hip_geom.so and libdvdgan_hip_sv.so for gfx950 (cross-compiles without a GPU).  Usage: build.sh [-j N]
 # Every compile also leaves build/<file>.res = hipcc's kernel-resource-usage remarks (registers, spills, scratch per kernel):
 # tests/test_abi_cpu.py holds the hot kernels to "no scratch" with it (a dynamically indexed accumulator array once put every
 # convolution kernel's accumulators into scratch memory: 3x on the step, invisible to every parity test).
@@ -88,3 +88,16 @@ for f in geom/*.hip; do
 done
 hipcc --offload-arch=gfx950 -shared -fPIC -o libdvdgan_hip_geom.so geom/build/*.o
 echo "built $(pwd)/libdvdgan_hip_geom.so"
+# libdvdgan_hip_sv.so (include/dvdgan_hip_sv.h): the seventh library, built the same way
+mkdir -p sv/build
+for f in sv/*.hip; do
+  o=sv/build/$(basename "${f%.hip}").o
+  r=sv/build/$(basename "${f%.hip}").res
+  if [ ! -f "$o" ] || [ ! -f "$r" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ ../../include/dvdgan_hip.h -nt "$o" ] || [ ../../include/dvdgan_hip_sv.h -nt "$o" ]; then
+    hipcc $FLAGS -c "$f" -o "$o" 2> "$r.tmp" || { cat "$r.tmp" >&2; rm -f "$o" "$r.tmp"; exit 1; }
+    grep -v "remark:\|^ *[0-9]* |\|^ *| *^" "$r.tmp" >&2 || true
+    grep "remark:" "$r.tmp" > "$r" || true; rm -f "$r.tmp"
+  fi
+done
+hipcc --offload-arch=gfx950 -shared -fPIC -o libdvdgan_hip_sv.so sv/build/*.o
+echo "built $(pwd)/libdvdgan_hip_sv.so"

@@ -383,6 +383,59 @@ def geom_check(code):
         raise RuntimeError(f"libdvdgan_hip_geom: {geom_lib().dvd_geom_strerror(code).decode()} (code {code})")
 
 
+# ---- libdvdgan_hip_sv.so (include/dvdgan_hip_sv.h): the top singular values of a table of weight matrices by block power
+# iteration (spectral.py), the seventh library with the same handshake (tests/test_sv_cpu.py compares the constants and the
+# table with the header and the exports with the table)
+SV_ABI_VERSION = 1
+SV_MAX_BLOCK, SV_MAX_SWEEPS, SV_MAX_ITEMS, SV_MAX_ITERS = 16, 60, 65535, 4096
+SV_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
+                       if name.startswith("SV_") and isinstance(value, int)}
+SV_SIGNATURES = {
+    "dvd_sv_abi_version": "i",
+    "dvd_sv_item_size": "i",
+    "dvd_sv_strerror": "s i",
+    "dvd_sv_prepare": "i pii pp",
+    "dvd_sv_init": "i ppii pp p",
+    "dvd_sv_iterate": "i ppii i p p",
+    "dvd_sv_ritz": "i ppii i ppp ll p",
+}
+SV_LIB_PATH = os.environ.get("DVD_SV_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_sv.so")
+_sv_lib = None
+
+
+class SvItem(C.Structure):              # == dvd_sv_item
+    _fields_ = [("W", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("state_off", C.c_longlong), ("ws_off", C.c_longlong),
+                ("h", C.c_int), ("w", C.c_int), ("slot", C.c_int), ("blk_wv", C.c_int), ("blk_wtv", C.c_int), ("pad_", C.c_int)]
+
+
+def sv_lib():
+    """The loaded libdvdgan_hip_sv.so, typed from SV_SIGNATURES.  Raises (never falls back) when it has not been built."""
+    global _sv_lib
+    if _sv_lib is None:
+        if not os.path.exists(SV_LIB_PATH):
+            raise RuntimeError(
+                f"{SV_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(dvd_gan_amd has no CPU / eager fallback)")
+        loaded = C.CDLL(SV_LIB_PATH)
+        for name, sig in SV_SIGNATURES.items():
+            fn = getattr(loaded, name, None)
+            if fn is None:
+                raise RuntimeError(f"libdvdgan_hip_sv.so exports no {name} -- lib.py and include/dvdgan_hip_sv.h disagree")
+            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
+        if loaded.dvd_sv_abi_version() != SV_ABI_VERSION:
+            raise RuntimeError("libdvdgan_hip_sv.so ABI version mismatch: rebuild it")
+        if loaded.dvd_sv_item_size() != C.sizeof(SvItem):
+            raise RuntimeError(f"libdvdgan_hip_sv.so: sizeof(dvd_sv_item) is {loaded.dvd_sv_item_size()}, the ctypes mirror SvItem has "
+                               f"{C.sizeof(SvItem)} bytes -- lib.py and include/dvdgan_hip_sv.h disagree")
+        _sv_lib = loaded
+    return _sv_lib
+
+
+def sv_check(code):
+    if code != 0:
+        raise RuntimeError(f"libdvdgan_hip_sv: {sv_lib().dvd_sv_strerror(code).decode()} (code {code})")
+
+
 ABI_VERSION = 13
 
 

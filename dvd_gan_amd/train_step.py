@@ -240,6 +240,23 @@ class Trainer(object):
         self._anchors = None          # fp32 [2 slots][D_s, D_t][real, fake] on the device, when lecam > 0
         self._adv_stats = None        # fp32 [6][lib.ADV_NSTAT]: D_s real / fake, D_t real / fake, G step D_s / D_t
         self._lecam_it = 0            # D iterations done
+        # singular-value monitoring of the weights (sv_log = 0 = off: no table, no workspace, no launch): every sv_log-th step
+        # sv_iters more block power iterations on each network's monitor and one row of its device ring of sv_log_rows rows; top
+        # sv_k values from blocks of sv_block columns, start blocks from a private generator seeded with sv_seed (spectral.py)
+        self.sv_log = int(getattr(c, "sv_log", 0) or 0)
+        self.sv_iters = int(getattr(c, "sv_iters", 4))
+        self.sv_log_rows = int(getattr(c, "sv_log_rows", 64))
+        self.sv_k = int(getattr(c, "sv_k", 3))
+        self.sv_block = int(getattr(c, "sv_block", 8))
+        self.sv_seed = int(getattr(c, "sv_seed", 0))
+        if (self.sv_log < 0 or not 1 <= self.sv_iters <= L.SV_MAX_ITERS or self.sv_log_rows < 1
+                or not 1 <= self.sv_k <= self.sv_block <= L.SV_MAX_BLOCK):
+            raise ValueError(f"sv_log={self.sv_log} (>= 0), sv_iters={self.sv_iters} (in [1, {L.SV_MAX_ITERS}]), "
+                             f"sv_log_rows={self.sv_log_rows} (>= 1), sv_k={self.sv_k}, sv_block={self.sv_block} "
+                             f"(1 <= sv_k <= sv_block <= {L.SV_MAX_BLOCK})")
+        self._sv = None               # {"G", "Ds", "Dt"} -> spectral.SpectrumMonitor, made at first use
+        self._sv_steps = 0            # steps this Trainer has taken
+        self._sv_logged = []          # step numbers of the rows logged so far
         self.lr_decay = getattr(c, "lr_decay", 0.9999)
         self.pretrained_model = getattr(c, "pretrained_model", None)
         self.model_save_path = os.path.join(getattr(c, "model_save_path", "./models"), getattr(c, "version", ""))
@@ -408,6 +425,74 @@ class Trainer(object):
         if not any(opt.guard for _, opt in self._optimizers()):
             return None
         return {tag: opt.guard_report() for tag, opt in self._optimizers()}
+
+    # ---- singular values of the weights (spectral.py)
+    def _sv_monitors(self):
+        """One monitor per network over every trainable tensor with dim() >= 2 (named by its state_dict key), with the layer's
+        weight_u / weight_v where it is spectrally normalised.  The ring's last row is sv_report()'s own."""
+        if self._sv is None:
+            from .spectral import SpectrumMonitor
+            self._sv = {}
+            for tag, net in (("G", self.G), ("Ds", self.D_s), ("Dt", self.D_t)):
+                prm = dict(net.named_parameters())
+                mats = [(n, p.data) for n, p in prm.items() if p.requires_grad and p.dim() >= 2]
+                sn = {}
+                for n, _ in mats:
+                    stem = n[:-len("weight_bar")] if n.endswith("weight_bar") else None
+                    if stem is not None and stem + "weight_u" in prm and stem + "weight_v" in prm:
+                        sn[n] = (prm[stem + "weight_u"].data, prm[stem + "weight_v"].data)
+                self._sv[tag] = SpectrumMonitor(mats, k=self.sv_k, block=self.sv_block, seed=self.sv_seed, sn=sn,
+                                                rows=self.sv_log_rows + 1)
+        return self._sv
+
+    def _sv_log_row(self):
+        row = len(self._sv_logged) % self.sv_log_rows
+        for mon in self._sv_monitors().values():
+            mon.update(self.sv_iters).snapshot(row)
+        self._sv_logged.append(self._sv_steps)
+
+    def sv_report(self, iters=None, reset=False):
+        """{"G", "Ds", "Dt"} -> list of {name, shape, sv, res, stable_rank, sn_sigma}, one entry per trainable tensor with
+        dim() >= 2: the top sv_k singular values of the tensor viewed [shape[0], -1] after `iters` (default config.sv_iters) more
+        iterations from the blocks the monitors hold (reset=True: from the seeded start blocks), their residuals, the stable rank
+        |W|_F^2 / sv[0]^2 and, for a spectrally normalised layer, sn_sigma = u^T W v of its weight_u / weight_v (else None):
+        sv[0] / sn_sigma says how far the normalisation lags behind the weights.  The values are Ritz values: lower bounds that
+        rise towards the singular values as the block converges (error ~ (sigma_{b+1} / sigma_i)^(2 iterations)), and for each of
+        them some singular value of W (or 0) lies within its `res`; see spectral.py.  The one call of this group that
+        synchronizes; works with sv_log = 0 too (the monitors are built at first use).  Reads the weights in place and changes
+        nothing: not the weights, the optimizer state, weight_u / weight_v, batch-norm statistics or any random stream.  The
+        blocks and the ring are a log, not training state: they are not in the state file, a resumed run starts them afresh."""
+        iters = self.sv_iters if iters is None else int(iters)
+        if iters < 0:
+            raise ValueError(f"iters={iters}")
+        mons = self._sv_monitors()
+        for mon in mons.values():
+            if reset:
+                mon.reset()
+            mon.update(iters).snapshot(self.sv_log_rows)
+        out = {}
+        for tag, mon in mons.items():
+            sv, res, fro2, sn = (t.tolist() for t in mon.split(mon.ring[self.sv_log_rows].cpu()))
+            out[tag] = [{"name": n, "shape": tuple(t.shape), "sv": sv[i], "res": res[i],
+                         "stable_rank": fro2[i] / sv[i][0] ** 2 if sv[i][0] > 0.0 else float("nan"),
+                         "sn_sigma": sn[i] if mon.sn[i] is not None else None}
+                        for i, (n, t) in enumerate(zip(mon.names, mon.tensors))]
+        return out
+
+    def sv_history(self):
+        """The rows config.sv_log has written, oldest first (the newest sv_log_rows of them): {"steps": [step of each row, counted
+        from this Trainer's first step = 1], "G" / "Ds" / "Dt": {"names", "sv" [rows, n, k], "res" [rows, n, k], "fro2" [rows, n],
+        "sn_sigma" [rows, n] (NaN without spectral norm)}} as host tensors.  Synchronizes.  None before the first logged row."""
+        if self._sv is None or not self._sv_logged:
+            return None
+        count, cap = len(self._sv_logged), self.sv_log_rows
+        order = [i % cap for i in range(max(0, count - cap), count)]
+        out = {"steps": self._sv_logged[-cap:]}
+        for tag, mon in self._sv.items():
+            rows, k = mon.ring[:cap].cpu()[order], mon.k
+            out[tag] = {"names": list(mon.names), "sv": rows[..., :k].contiguous(), "res": rows[..., k:2 * k].contiguous(),
+                        "fro2": rows[..., 2 * k].contiguous(), "sn_sigma": rows[..., 2 * k + 1].contiguous()}
+        return out
 
     def _sync_replicas(self):
         D.broadcast_state((self.G, self.D_s, self.D_t),
@@ -697,6 +782,10 @@ class Trainer(object):
         self.g_lr_scher.step((g_s_loss + g_t_loss) if self._plateau else None)
         if aug or geo:
             self._aug_adapt()
+        if getattr(self, "sv_log", 0):
+            self._sv_steps += 1
+            if self._sv_steps % self.sv_log == 0:
+                self._sv_log_row()
         return ds_loss_real, ds_loss_fake, dt_loss_real, dt_loss_fake, g_s_loss, g_t_loss
 
     # ---- trainer.py:189-343 (loop; logging reduced to a print)
