@@ -4,9 +4,9 @@ two launches of libdvdgan_hip_aug.so (include/dvdgan_hip_aug.h states the arithm
 the host, wraps the launches for autograd and holds the rule that moves p.  Every frame of a clip shares one parameter row: a
 video discriminator must not see the transform flicker from frame to frame."""
 import torch
-from torch.autograd import Function
 
 from . import lib as L
+from .clip_op import clip_op
 
 POLICIES = ("color", "translation", "cutout")
 IDENTITY_ROW = (0.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)       # b, s, c, dx, dy, cy0, cx0, ch, cw
@@ -57,50 +57,24 @@ def draw_params(B, H, W, policy, p, generator=None):
     return out.float()
 
 
-def _launch(fn, src, params, frames_per_clip):
-    """One launch over src [N, 3, H, W] (contiguous fp32 on the device) -> a new tensor of the same shape."""
-    if src.dtype != torch.float32 or not src.is_cuda or src.dim() != 4 or src.shape[1] != 3:
-        raise ValueError(f"clip augmentation takes device fp32 frames [N, 3, H, W], got {src.dtype} {tuple(src.shape)}")
-    N, _, H, W = src.shape
-    clips = -(-N // frames_per_clip)
-    if (params.dtype != torch.float32 or params.device != src.device or tuple(params.shape) != (clips, L.AUG_COLS)
-            or not params.is_contiguous()):
-        raise ValueError(f"clip augmentation: the parameter table must be a contiguous device fp32 [{clips}, {L.AUG_COLS}], got "
-                         f"{params.dtype} {tuple(params.shape)} on {params.device}")
-    dst = torch.empty_like(src)
-    L.aug_check(fn(L.ptr(src), L.ptr(dst), L.ptr(params), N, int(frames_per_clip), H, W, L.stream()))
-    return dst
+_forward, _backward, _ClipOp = clip_op("ClipAugment", L.aug_lib, "dvd_aug_clip_forward", "dvd_aug_clip_backward", L.aug_check,
+                                       L.AUG_COLS, "clip augmentation", "the parameter table")
 
 
 def clip_forward(frames, params, frames_per_clip):
     """frames [N, 3, H, W] fp32 on the device, frame n of clip n // frames_per_clip; params [clips, lib.AUG_COLS] -> the
     transformed frames (dvd_aug_clip_forward).  No autograd."""
-    return _launch(L.aug_lib().dvd_aug_clip_forward, frames.contiguous(), params, frames_per_clip)
+    return _forward(frames, params, frames_per_clip)
 
 
 def clip_backward(grad, params, frames_per_clip):
     """The transpose of clip_forward applied to grad (dvd_aug_clip_backward)."""
-    return _launch(L.aug_lib().dvd_aug_clip_backward, grad.contiguous(), params, frames_per_clip)
+    return _backward(grad, params, frames_per_clip)
 
 
-class ClipAugment(Function):
+class ClipAugment(_ClipOp):
     """apply(frames5d [B, T, 3, H, W], params [B, lib.AUG_COLS] on the device) -> the augmented clips.  The map is affine in the
     frames, so only `params` is saved; the table receives no gradient."""
-
-    @staticmethod
-    def forward(ctx, frames, params):
-        if frames.dim() != 5:
-            raise ValueError(f"ClipAugment takes clips [B, T, 3, H, W], got {tuple(frames.shape)}")
-        B, T = frames.shape[:2]
-        ctx.save_for_backward(params)
-        out = clip_forward(frames.contiguous().view(B * T, *frames.shape[2:]), params, T)
-        return out.view(frames.shape)
-
-    @staticmethod
-    def backward(ctx, g):
-        (params,) = ctx.saved_tensors
-        B, T = g.shape[:2]
-        return clip_backward(g.contiguous().view(B * T, *g.shape[2:]), params, T).view(g.shape), None
 
 
 def ada_update(p, r_t, target, batch, interval, kimg):

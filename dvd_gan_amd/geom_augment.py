@@ -6,9 +6,9 @@ frame of a clip shares one row, as in augment.py, whose probability p and privat
 import math
 
 import torch
-from torch.autograd import Function
 
 from . import lib as L
+from .clip_op import clip_op
 
 GEOM_POLICIES = ("xflip", "rot90", "scale", "rotate", "aniso")
 IDENTITY_ROW = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)       # a00, a01, a02, a10, a11, a12
@@ -84,47 +84,21 @@ def draw_geom(B, H, W, policy, p, generator=None):
     return (out + 0.0).float()                       # (+ 0.0: no negative zeros in the table)
 
 
-def _launch(fn, src, mats, frames_per_clip):
-    """One launch over src [N, 3, H, W] (contiguous fp32 on the device) -> a new tensor of the same shape."""
-    if src.dtype != torch.float32 or not src.is_cuda or src.dim() != 4 or src.shape[1] != 3:
-        raise ValueError(f"the clip warp takes device fp32 frames [N, 3, H, W], got {src.dtype} {tuple(src.shape)}")
-    N, _, H, W = src.shape
-    clips = -(-N // frames_per_clip)
-    if (mats.dtype != torch.float32 or mats.device != src.device or tuple(mats.shape) != (clips, L.GEOM_COLS)
-            or not mats.is_contiguous()):
-        raise ValueError(f"the clip warp: the table must be a contiguous device fp32 [{clips}, {L.GEOM_COLS}], got "
-                         f"{mats.dtype} {tuple(mats.shape)} on {mats.device}")
-    dst = torch.empty_like(src)
-    L.geom_check(fn(L.ptr(src), L.ptr(dst), L.ptr(mats), N, int(frames_per_clip), H, W, L.stream()))
-    return dst
+_forward, _backward, _ClipOp = clip_op("ClipWarp", L.geom_lib, "dvd_geom_clip_forward", "dvd_geom_clip_backward", L.geom_check,
+                                       L.GEOM_COLS, "the clip warp", "the table")
 
 
 def clip_warp_forward(frames, mats, frames_per_clip):
     """frames [N, 3, H, W] fp32 on the device, frame n of clip n // frames_per_clip; mats [clips, lib.GEOM_COLS] -> the warped
     frames (dvd_geom_clip_forward).  No autograd."""
-    return _launch(L.geom_lib().dvd_geom_clip_forward, frames.contiguous(), mats, frames_per_clip)
+    return _forward(frames, mats, frames_per_clip)
 
 
 def clip_warp_backward(grad, mats, frames_per_clip):
     """The transpose of clip_warp_forward applied to grad (dvd_geom_clip_backward)."""
-    return _launch(L.geom_lib().dvd_geom_clip_backward, grad.contiguous(), mats, frames_per_clip)
+    return _backward(grad, mats, frames_per_clip)
 
 
-class ClipWarp(Function):
+class ClipWarp(_ClipOp):
     """apply(frames5d [B, T, 3, H, W], mats [B, lib.GEOM_COLS] on the device) -> the warped clips.  The map is linear in the frames,
     so only `mats` is saved; the table receives no gradient."""
-
-    @staticmethod
-    def forward(ctx, frames, mats):
-        if frames.dim() != 5:
-            raise ValueError(f"ClipWarp takes clips [B, T, 3, H, W], got {tuple(frames.shape)}")
-        B, T = frames.shape[:2]
-        ctx.save_for_backward(mats)
-        out = clip_warp_forward(frames.contiguous().view(B * T, *frames.shape[2:]), mats, T)
-        return out.view(frames.shape)
-
-    @staticmethod
-    def backward(ctx, g):
-        (mats,) = ctx.saved_tensors
-        B, T = g.shape[:2]
-        return clip_warp_backward(g.contiguous().view(B * T, *g.shape[2:]), mats, T).view(g.shape), None

@@ -1,6 +1,8 @@
-"""ctypes binding of libdvdgan_hip.so (include/dvdgan_hip.h).  Fails loudly: no fallback."""
+"""ctypes binding of the shared libraries csrc/build.sh makes, one per header under include/: LIBRARIES (at the end) is the table of
+them, _load() the one handshake.  Fails loudly: no fallback."""
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -28,8 +30,6 @@ HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items
                     if name.isupper() and not name.startswith("_") and isinstance(value, int)}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVD_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip.so")    # (override: A/B builds)
-_lib = None
 
 
 class ConvDesc(C.Structure):
@@ -152,37 +152,9 @@ SIGNATURES = {
 }
 
 
-def lib():
-    """The loaded shared library.  Raises (never falls back) when it has not been built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(dvd_gan_amd has no CPU / eager fallback)")
-        _lib = C.CDLL(LIB_PATH)
-        if _lib.dvd_abi_version() != ABI_VERSION:
-            raise RuntimeError("libdvdgan_hip.so ABI version mismatch: rebuild it")
-        # signature handshake: every entry point gets its declared types, so a plain Python int reaches a `long long` whole
-        for name, sig in SIGNATURES.items():
-            fn = getattr(_lib, name, None)
-            if fn is None:
-                _lib = None
-                raise RuntimeError(f"libdvdgan_hip.so exports no {name} -- lib.py and include/dvdgan_hip.h disagree")
-            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
-        # layout handshake: every descriptor mirror below must have the size the library was compiled with
-        for which, mirror in STRUCT_MIRRORS.items():
-            want = _lib.dvd_struct_size(which)
-            if want != C.sizeof(mirror):
-                _lib = None
-                raise RuntimeError(f"libdvdgan_hip.so: sizeof descriptor {which} is {want}, the ctypes mirror {mirror.__name__} has "
-                                   f"{C.sizeof(mirror)} bytes -- lib.py and include/dvdgan_hip.h disagree")
-    return _lib
-
-
-# ---- libdvdgan_hip_adv.so (include/dvdgan_hip_adv.h): the loss launch with LeCam regularization, top-k selection and logit
-# statistics, a library of its own with the same handshake -- every `#define DVD_ADV_*` of its header by name, one line of
-# type codes per entry point (tests/test_adv_ref_cpu.py compares both with the header and the exports with the table)
+# ---- The side libraries, each with a header of its own: every `#define DVD_<KEY>_*` of the header by name, one line of type codes
+# per entry point (tests/test_abi_cpu.py compares both with the header and the exports with the table, library by library).
+# libdvdgan_hip_adv.so (include/dvdgan_hip_adv.h): the loss launch with LeCam regularization, top-k selection and logit statistics
 ADV_MAX_SAMPLES, ADV_NSTAT = 4096, 8        # samples a selection serves, floats of the statistics
 (ADV_STAT_MEAN, ADV_STAT_SIGN, ADV_STAT_ACTIVE, ADV_STAT_ADV, ADV_STAT_LECAM, ADV_STAT_ANCHOR, ADV_STAT_KEPT,
  ADV_STAT_NONFINITE) = range(ADV_NSTAT)
@@ -191,31 +163,9 @@ ADV_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().i
 ADV_SIGNATURES = {
     "dvd_adv_loss_ex": "i p l iiii f ppp f pp f p p",
 }
-ADV_LIB_PATH = os.environ.get("DVD_ADV_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_adv.so")
-_adv_lib = None
 
-
-def adv_lib():
-    """The loaded libdvdgan_hip_adv.so, typed from ADV_SIGNATURES.  Raises (never falls back) when it has not been built."""
-    global _adv_lib
-    if _adv_lib is None:
-        if not os.path.exists(ADV_LIB_PATH):
-            raise RuntimeError(
-                f"{ADV_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(dvd_gan_amd has no CPU / eager fallback)")
-        loaded = C.CDLL(ADV_LIB_PATH)
-        for name, sig in ADV_SIGNATURES.items():
-            fn = getattr(loaded, name, None)
-            if fn is None:
-                raise RuntimeError(f"libdvdgan_hip_adv.so exports no {name} -- lib.py and include/dvdgan_hip_adv.h disagree")
-            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
-        _adv_lib = loaded
-    return _adv_lib
-
-
-# ---- libdvdgan_hip_eval.so (include/dvdgan_hip_eval.h): pooled features, running moments and kernel distances of sample
-# features (distmetrics.py), the third library with the same handshake (tests/test_distmetrics_cpu.py compares the constants and
-# the table with the header and the exports with the table)
+# libdvdgan_hip_eval.so (include/dvdgan_hip_eval.h): pooled features, running moments and kernel distances of sample features
+# (distmetrics.py)
 EVAL_MAX_D, EVAL_TILE, EVAL_MAX_SUBSETS = 4096, 64, 65535
 EVAL_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
                          if name.startswith("EVAL_") and isinstance(value, int)}
@@ -227,36 +177,9 @@ EVAL_SIGNATURES = {
     "dvd_eval_kid_ws_doubles": "l ii",
     "dvd_eval_kid": "i pll pll i pppp ii ppp p",
 }
-EVAL_LIB_PATH = os.environ.get("DVD_EVAL_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_eval.so")
-_eval_lib = None
 
-
-def eval_lib():
-    """The loaded libdvdgan_hip_eval.so, typed from EVAL_SIGNATURES.  Raises (never falls back) when it has not been built."""
-    global _eval_lib
-    if _eval_lib is None:
-        if not os.path.exists(EVAL_LIB_PATH):
-            raise RuntimeError(
-                f"{EVAL_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(dvd_gan_amd has no CPU / eager fallback)")
-        loaded = C.CDLL(EVAL_LIB_PATH)
-        for name, sig in EVAL_SIGNATURES.items():
-            fn = getattr(loaded, name, None)
-            if fn is None:
-                raise RuntimeError(f"libdvdgan_hip_eval.so exports no {name} -- lib.py and include/dvdgan_hip_eval.h disagree")
-            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
-        _eval_lib = loaded
-    return _eval_lib
-
-
-def eval_check(code):
-    if code != 0:
-        raise RuntimeError(f"libdvdgan_hip_eval: {eval_lib().dvd_eval_strerror(code).decode()} (code {code})")
-
-
-# ---- libdvdgan_hip_prdc.so (include/dvdgan_hip_prdc.h): k-nearest-neighbour radii and ball counts of sample features (precision /
-# recall / density / coverage, distmetrics.py), the fourth library with the same handshake (tests/test_prdc_cpu.py compares the
-# constants and the table with the header and the exports with the table)
+# libdvdgan_hip_prdc.so (include/dvdgan_hip_prdc.h): k-nearest-neighbour radii and ball counts of sample features (precision /
+# recall / density / coverage, distmetrics.py)
 PRDC_MAX_D, PRDC_MAX_K, PRDC_TILE, PRDC_MAX_ROWS = 4096, 16, 64, 1 << 24
 PRDC_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
                          if name.startswith("PRDC_") and isinstance(value, int)}
@@ -268,36 +191,9 @@ PRDC_SIGNATURES = {
     "dvd_prdc_ball_ws_doubles": "l ll",
     "dvd_prdc_ball_count": "i pll pll i p p p pp p",
 }
-PRDC_LIB_PATH = os.environ.get("DVD_PRDC_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_prdc.so")
-_prdc_lib = None
 
-
-def prdc_lib():
-    """The loaded libdvdgan_hip_prdc.so, typed from PRDC_SIGNATURES.  Raises (never falls back) when it has not been built."""
-    global _prdc_lib
-    if _prdc_lib is None:
-        if not os.path.exists(PRDC_LIB_PATH):
-            raise RuntimeError(
-                f"{PRDC_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(dvd_gan_amd has no CPU / eager fallback)")
-        loaded = C.CDLL(PRDC_LIB_PATH)
-        for name, sig in PRDC_SIGNATURES.items():
-            fn = getattr(loaded, name, None)
-            if fn is None:
-                raise RuntimeError(f"libdvdgan_hip_prdc.so exports no {name} -- lib.py and include/dvdgan_hip_prdc.h disagree")
-            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
-        _prdc_lib = loaded
-    return _prdc_lib
-
-
-def prdc_check(code):
-    if code != 0:
-        raise RuntimeError(f"libdvdgan_hip_prdc: {prdc_lib().dvd_prdc_strerror(code).decode()} (code {code})")
-
-
-# ---- libdvdgan_hip_aug.so (include/dvdgan_hip_aug.h): clip-consistent augmentation of the discriminators' inputs and its
-# transpose (augment.py), the fifth library with the same handshake (tests/test_aug_cpu.py compares the constants and the table
-# with the header and the exports with the table)
+# libdvdgan_hip_aug.so (include/dvdgan_hip_aug.h): clip-consistent augmentation of the discriminators' inputs and its transpose
+# (augment.py)
 AUG_ABI_VERSION = 1
 AUG_COLS = 9
 (AUG_B, AUG_S, AUG_C, AUG_DX, AUG_DY, AUG_CY0, AUG_CX0, AUG_CH, AUG_CW) = range(AUG_COLS)
@@ -310,38 +206,9 @@ AUG_SIGNATURES = {
     "dvd_aug_clip_forward": "i ppp liii p",
     "dvd_aug_clip_backward": "i ppp liii p",
 }
-AUG_LIB_PATH = os.environ.get("DVD_AUG_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_aug.so")
-_aug_lib = None
 
-
-def aug_lib():
-    """The loaded libdvdgan_hip_aug.so, typed from AUG_SIGNATURES.  Raises (never falls back) when it has not been built."""
-    global _aug_lib
-    if _aug_lib is None:
-        if not os.path.exists(AUG_LIB_PATH):
-            raise RuntimeError(
-                f"{AUG_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(dvd_gan_amd has no CPU / eager fallback)")
-        loaded = C.CDLL(AUG_LIB_PATH)
-        for name, sig in AUG_SIGNATURES.items():
-            fn = getattr(loaded, name, None)
-            if fn is None:
-                raise RuntimeError(f"libdvdgan_hip_aug.so exports no {name} -- lib.py and include/dvdgan_hip_aug.h disagree")
-            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
-        if loaded.dvd_aug_abi_version() != AUG_ABI_VERSION:
-            raise RuntimeError("libdvdgan_hip_aug.so ABI version mismatch: rebuild it")
-        _aug_lib = loaded
-    return _aug_lib
-
-
-def aug_check(code):
-    if code != 0:
-        raise RuntimeError(f"libdvdgan_hip_aug: {aug_lib().dvd_aug_strerror(code).decode()} (code {code})")
-
-
-# ---- libdvdgan_hip_geom.so (include/dvdgan_hip_geom.h): the clip-consistent affine warp of the discriminators' inputs and its
-# transpose (geom_augment.py), the sixth library with the same handshake (tests/test_geom_cpu.py compares the constants and the
-# table with the header and the exports with the table)
+# libdvdgan_hip_geom.so (include/dvdgan_hip_geom.h): the clip-consistent affine warp of the discriminators' inputs and its
+# transpose (geom_augment.py)
 GEOM_ABI_VERSION = 1
 GEOM_COLS = 6
 (GEOM_A00, GEOM_A01, GEOM_A02, GEOM_A10, GEOM_A11, GEOM_A12) = range(GEOM_COLS)
@@ -354,38 +221,9 @@ GEOM_SIGNATURES = {
     "dvd_geom_clip_forward": "i ppp liii p",
     "dvd_geom_clip_backward": "i ppp liii p",
 }
-GEOM_LIB_PATH = os.environ.get("DVD_GEOM_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_geom.so")
-_geom_lib = None
 
-
-def geom_lib():
-    """The loaded libdvdgan_hip_geom.so, typed from GEOM_SIGNATURES.  Raises (never falls back) when it has not been built."""
-    global _geom_lib
-    if _geom_lib is None:
-        if not os.path.exists(GEOM_LIB_PATH):
-            raise RuntimeError(
-                f"{GEOM_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(dvd_gan_amd has no CPU / eager fallback)")
-        loaded = C.CDLL(GEOM_LIB_PATH)
-        for name, sig in GEOM_SIGNATURES.items():
-            fn = getattr(loaded, name, None)
-            if fn is None:
-                raise RuntimeError(f"libdvdgan_hip_geom.so exports no {name} -- lib.py and include/dvdgan_hip_geom.h disagree")
-            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
-        if loaded.dvd_geom_abi_version() != GEOM_ABI_VERSION:
-            raise RuntimeError("libdvdgan_hip_geom.so ABI version mismatch: rebuild it")
-        _geom_lib = loaded
-    return _geom_lib
-
-
-def geom_check(code):
-    if code != 0:
-        raise RuntimeError(f"libdvdgan_hip_geom: {geom_lib().dvd_geom_strerror(code).decode()} (code {code})")
-
-
-# ---- libdvdgan_hip_sv.so (include/dvdgan_hip_sv.h): the top singular values of a table of weight matrices by block power
-# iteration (spectral.py), the seventh library with the same handshake (tests/test_sv_cpu.py compares the constants and the
-# table with the header and the exports with the table)
+# libdvdgan_hip_sv.so (include/dvdgan_hip_sv.h): the top singular values of a table of weight matrices by block power iteration
+# (spectral.py)
 SV_ABI_VERSION = 1
 SV_MAX_BLOCK, SV_MAX_SWEEPS, SV_MAX_ITEMS, SV_MAX_ITERS = 16, 60, 65535, 4096
 SV_HEADER_CONSTANTS = {"DVD_" + name: value for name, value in list(globals().items())
@@ -399,41 +237,11 @@ SV_SIGNATURES = {
     "dvd_sv_iterate": "i ppii i p p",
     "dvd_sv_ritz": "i ppii i ppp ll p",
 }
-SV_LIB_PATH = os.environ.get("DVD_SV_LIB_PATH") or os.path.join(_HERE, "csrc", "libdvdgan_hip_sv.so")
-_sv_lib = None
 
 
 class SvItem(C.Structure):              # == dvd_sv_item
     _fields_ = [("W", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("state_off", C.c_longlong), ("ws_off", C.c_longlong),
                 ("h", C.c_int), ("w", C.c_int), ("slot", C.c_int), ("blk_wv", C.c_int), ("blk_wtv", C.c_int), ("pad_", C.c_int)]
-
-
-def sv_lib():
-    """The loaded libdvdgan_hip_sv.so, typed from SV_SIGNATURES.  Raises (never falls back) when it has not been built."""
-    global _sv_lib
-    if _sv_lib is None:
-        if not os.path.exists(SV_LIB_PATH):
-            raise RuntimeError(
-                f"{SV_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(dvd_gan_amd has no CPU / eager fallback)")
-        loaded = C.CDLL(SV_LIB_PATH)
-        for name, sig in SV_SIGNATURES.items():
-            fn = getattr(loaded, name, None)
-            if fn is None:
-                raise RuntimeError(f"libdvdgan_hip_sv.so exports no {name} -- lib.py and include/dvdgan_hip_sv.h disagree")
-            fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
-        if loaded.dvd_sv_abi_version() != SV_ABI_VERSION:
-            raise RuntimeError("libdvdgan_hip_sv.so ABI version mismatch: rebuild it")
-        if loaded.dvd_sv_item_size() != C.sizeof(SvItem):
-            raise RuntimeError(f"libdvdgan_hip_sv.so: sizeof(dvd_sv_item) is {loaded.dvd_sv_item_size()}, the ctypes mirror SvItem has "
-                               f"{C.sizeof(SvItem)} bytes -- lib.py and include/dvdgan_hip_sv.h disagree")
-        _sv_lib = loaded
-    return _sv_lib
-
-
-def sv_check(code):
-    if code != 0:
-        raise RuntimeError(f"libdvdgan_hip_sv: {sv_lib().dvd_sv_strerror(code).decode()} (code {code})")
 
 
 ABI_VERSION = 13
@@ -442,7 +250,7 @@ ABI_VERSION = 13
 def check(code):
     if code != 0:
         reset_gru_tickets()           # a failed / aborted launch may have left split-K tickets behind: the next one must start from zero
-        raise RuntimeError(f"libdvdgan_hip: {lib().dvd_strerror(code).decode()} (code {code})")
+        _fail("core", code)
 
 
 def dt(t):
@@ -532,3 +340,119 @@ class FragItem(C.Structure):            # == dvd_frag_item
 # dvd_struct_size(which) -> ctypes mirror (DVD_STRUCT_* of include/dvdgan_hip.h)
 STRUCT_MIRRORS = {STRUCT_CONV: ConvDesc, STRUCT_WGRAD: WgradDesc, STRUCT_GRU: GruDesc, STRUCT_SN_ITEM: SnItem,
                   STRUCT_GRU_STACK: GruStackDesc, STRUCT_PACK_ITEM: PackItem, STRUCT_FRAG_ITEM: FragItem}
+
+
+class Library(NamedTuple):
+    """One shared library and its published header: everything _load() checks.  so, env and header follow csrc/build.sh's
+    convention -- csrc/<key>/*.hip -> libdvdgan_hip_<key>.so, declared by include/dvdgan_hip_<key>.h; the top level is "core"."""
+    so: str                 # file name under csrc/
+    env: str                # environment variable that overrides the path (A/B builds)
+    header: str             # file name under include/
+    signatures: dict        # entry point -> type codes (_CTYPES)
+    constants: dict         # `#define` of the header -> value
+    abi: tuple = None       # (version function, the value it must return)
+    structs: object = None  # loaded handle -> [(what, its size as the library was compiled, ctypes mirror)]
+    strerror: str = None    # the function that words a return code
+
+
+def _library(key, signatures, constants, **handshake):
+    tag = "" if key == "core" else "_" + key
+    return Library(f"libdvdgan_hip{tag}.so", f"DVD{tag.upper()}_LIB_PATH", f"dvdgan_hip{tag}.h", signatures, constants, **handshake)
+
+
+# Adding a library: a directory csrc/<key>/ of .hip files, include/dvdgan_hip_<key>.h and one entry here (tests/test_abi_cpu.py
+# holds the three to one another and runs the whole handshake test over the new key).
+LIBRARIES = {
+    "core": _library("core", SIGNATURES, HEADER_CONSTANTS, abi=("dvd_abi_version", ABI_VERSION), strerror="dvd_strerror",
+                     structs=lambda so: [(f"sizeof descriptor {which}", so.dvd_struct_size(which), mirror)
+                                         for which, mirror in STRUCT_MIRRORS.items()]),
+    "adv": _library("adv", ADV_SIGNATURES, ADV_HEADER_CONSTANTS),
+    "eval": _library("eval", EVAL_SIGNATURES, EVAL_HEADER_CONSTANTS, strerror="dvd_eval_strerror"),
+    "prdc": _library("prdc", PRDC_SIGNATURES, PRDC_HEADER_CONSTANTS, strerror="dvd_prdc_strerror"),
+    "aug": _library("aug", AUG_SIGNATURES, AUG_HEADER_CONSTANTS, abi=("dvd_aug_abi_version", AUG_ABI_VERSION),
+                    strerror="dvd_aug_strerror"),
+    "geom": _library("geom", GEOM_SIGNATURES, GEOM_HEADER_CONSTANTS, abi=("dvd_geom_abi_version", GEOM_ABI_VERSION),
+                     strerror="dvd_geom_strerror"),
+    "sv": _library("sv", SV_SIGNATURES, SV_HEADER_CONSTANTS, abi=("dvd_sv_abi_version", SV_ABI_VERSION), strerror="dvd_sv_strerror",
+                   structs=lambda so: [("sizeof(dvd_sv_item)", so.dvd_sv_item_size(), SvItem)]),
+}
+_handles = {}           # key -> checked handle; _handles.pop(key, None) drops one, and the next accessor call loads it again
+
+
+def library_path(key):
+    """Where LIBRARIES[key] is loaded from: its environment variable, read now, or csrc/ of this tree."""
+    return os.environ.get(LIBRARIES[key].env) or os.path.join(_HERE, "csrc", LIBRARIES[key].so)
+
+
+def _load(key):
+    """The loaded LIBRARIES[key].  The first call dlopens it and runs its whole handshake; the handle is published only after
+    every check has passed.  Raises (never falls back) when the library has not been built or disagrees with this file."""
+    if key in _handles:
+        return _handles[key]
+    rec, path = LIBRARIES[key], library_path(key)
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                           "(dvd_gan_amd has no CPU / eager fallback)")
+    loaded = C.CDLL(path)
+    # ABI handshake first: a stale build is told to rebuild, not that one of its entry points is missing
+    if rec.abi and hasattr(loaded, rec.abi[0]) and getattr(loaded, rec.abi[0])() != rec.abi[1]:
+        raise RuntimeError(f"{rec.so} ABI version mismatch: rebuild it")
+    # signature handshake: every entry point gets its declared types, so a plain Python int reaches a `long long` whole
+    for name, sig in rec.signatures.items():
+        fn = getattr(loaded, name, None)
+        if fn is None:
+            raise RuntimeError(f"{rec.so} exports no {name} -- lib.py and include/{rec.header} disagree")
+        fn.restype, fn.argtypes = _CTYPES[sig[0]], [_CTYPES[a] for a in sig[1:].replace(" ", "")]
+    # layout handshake: every struct mirror must have the size the library was compiled with
+    for what, size, mirror in (rec.structs(loaded) if rec.structs else ()):
+        if size != C.sizeof(mirror):
+            raise RuntimeError(f"{rec.so}: {what} is {size}, the ctypes mirror {mirror.__name__} has {C.sizeof(mirror)} bytes "
+                               f"-- lib.py and include/{rec.header} disagree")
+    _handles[key] = loaded
+    return loaded
+
+
+def load_all():
+    """Every library of the table, loaded and checked (what __graft_entry__.build() ends with)."""
+    return [_load(key) for key in LIBRARIES]
+
+
+def _fail(key, code):
+    rec = LIBRARIES[key]
+    raise RuntimeError(f"{rec.so[:-3]}: {getattr(_load(key), rec.strerror)(code).decode()} (code {code})")
+
+
+def _checker(key):
+    def check_code(code):
+        if code != 0:                   # (once per launch: nothing but this test when the call succeeded)
+            _fail(key, code)
+    return check_code
+
+
+def _accessor(key):
+    def handle():
+        try:                            # once per launch on the hot path: one dict subscript when loaded
+            return _handles[key]
+        except KeyError:
+            return _load(key)
+    handle.__doc__ = f"The loaded {LIBRARIES[key].so}, typed from its signature table.  Raises (never falls back) when it has not been built."
+    return handle
+
+
+# The accessors and checks call sites use: one view of the table each.
+lib = _accessor("core")
+adv_lib = _accessor("adv")
+eval_lib = _accessor("eval")
+prdc_lib = _accessor("prdc")
+aug_lib = _accessor("aug")
+geom_lib = _accessor("geom")
+sv_lib = _accessor("sv")
+eval_check = _checker("eval")
+prdc_check = _checker("prdc")
+aug_check = _checker("aug")
+geom_check = _checker("geom")
+sv_check = _checker("sv")
+
+
+# the paths as this import found them (tools and tests that inspect the files)
+LIB_PATH, ADV_LIB_PATH, EVAL_LIB_PATH, PRDC_LIB_PATH, AUG_LIB_PATH, GEOM_LIB_PATH, SV_LIB_PATH = map(library_path, LIBRARIES)

@@ -1,6 +1,7 @@
 """CPU checks of the C-ABI library: it loads, exports every symbol include/dvdgan_hip.h declares, reports
 its ABI version, validates arguments without touching a GPU, and the Python host layer reproduces the
-reference state_dict layout.  (No compute calls: there is no GPU in this tier.)"""
+reference state_dict layout; the same handshake of every side library of lib.LIBRARIES against its own header, and the table
+against the directories and headers of the tree.  (No compute calls: there is no GPU in this tier.)"""
 import ctypes
 import os
 import re
@@ -31,7 +32,7 @@ def test_library_exports_every_declared_symbol():
     import shutil
     import subprocess
     if shutil.which("nm"):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH]).decode()
+        out = subprocess.check_output(["nm", "-D", "--defined-only", L.library_path("core")]).decode()
         # EVERY defined text symbol, whatever its name (C++ helpers and kernel stubs included): -fvisibility=hidden + the
         # header's visibility pragma leave exactly the declared entry points (_init / _fini come from the C runtime)
         exported = sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1] not in ("_init", "_fini"))
@@ -66,12 +67,13 @@ def test_descriptor_layouts_match_the_library():
         _fields_ = L.ConvDesc._fields_[:-2]
     try:
         L.STRUCT_MIRRORS[0] = Short
-        L._lib = None
+        L._handles.pop("core", None)
         with pytest.raises(RuntimeError, match="sizeof descriptor 0"):
             L.lib()
+        assert "core" not in L._handles                                   # a half-checked handle is never published
     finally:
         L.STRUCT_MIRRORS[0] = saved
-        L._lib = None
+        L._handles.pop("core", None)
         L.lib()
 
 
@@ -145,13 +147,123 @@ def test_loaded_library_is_fully_typed():
     # a table line without a function in the library is refused at load
     try:
         L.SIGNATURES["dvd_no_such_entry"] = "i p"
-        L._lib = None
+        L._handles.pop("core", None)
         with pytest.raises(RuntimeError, match="exports no dvd_no_such_entry"):
             L.lib()
+        assert "core" not in L._handles
     finally:
         del L.SIGNATURES["dvd_no_such_entry"]
-        L._lib = None
+        L._handles.pop("core", None)
         L.lib()
+
+
+# ------------------------------------------------------------------ the side libraries: one handshake, library by library
+SIDE_LIBRARIES = {      # key of lib.LIBRARIES -> the entry points its header declares, the number of its #defines
+    "adv": (["dvd_adv_loss_ex"], 10),
+    "eval": (["dvd_eval_strerror", "dvd_eval_pool_features", "dvd_eval_moments_state_doubles", "dvd_eval_moments_update",
+              "dvd_eval_kid_ws_doubles", "dvd_eval_kid"], 3),
+    "prdc": (["dvd_prdc_strerror", "dvd_prdc_column_mean", "dvd_prdc_knn_ws_doubles", "dvd_prdc_knn_radii",
+              "dvd_prdc_ball_ws_doubles", "dvd_prdc_ball_count"], 4),
+    "aug": (["dvd_aug_abi_version", "dvd_aug_strerror", "dvd_aug_clip_forward", "dvd_aug_clip_backward"], 14),
+    "geom": (["dvd_geom_abi_version", "dvd_geom_strerror", "dvd_geom_clip_forward", "dvd_geom_clip_backward"], 11),
+    "sv": (["dvd_sv_abi_version", "dvd_sv_item_size", "dvd_sv_strerror", "dvd_sv_prepare", "dvd_sv_init", "dvd_sv_iterate",
+            "dvd_sv_ritz"], 5),
+}
+
+
+@pytest.mark.parametrize("key", sorted(SIDE_LIBRARIES))
+def test_side_library_handshake(key):
+    """libdvdgan_hip_<key>.so against include/dvdgan_hip_<key>.h, the checks made of the core library above, with the same parser:
+    the library exports exactly the header's declarations, the signature table says what the prototypes say and types every loaded
+    function, the constants dict holds every #define of the header by name and value, the ABI version (where the library has
+    one) is the expected one, and a table line without a function in the library is refused at load."""
+    import shutil
+    import subprocess
+    from dvd_gan_amd import lib as L
+    rec = L.LIBRARIES[key]
+    names, n_defines = SIDE_LIBRARIES[key]
+    assert (rec.so, rec.header) == (f"libdvdgan_hip_{key}.so", f"dvdgan_hip_{key}.h")
+    header = os.path.join(ROOT, "include", rec.header)
+    text = open(header).read()
+    want = declared_signatures(header)
+    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert sorted(want) == sorted(set(re.findall(r"\b(dvd_[a-z0-9_]+)\s*\(", src))) == sorted(names)
+    assert {n: sig.replace(" ", "") for n, sig in rec.signatures.items()} == want
+    loaded = L._load(key)
+    for name, sig in rec.signatures.items():
+        fn, sig = getattr(loaded, name), sig.replace(" ", "")
+        assert fn.restype is L._CTYPES[sig[0]] and list(fn.argtypes) == [L._CTYPES[c] for c in sig[1:]], name
+    if shutil.which("nm"):
+        out = subprocess.check_output(["nm", "-D", "--defined-only", L.library_path(key)]).decode()
+        exported = sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1] not in ("_init", "_fini"))
+        assert exported == sorted(want), exported
+    defines = {n: int(v) for n, v in re.findall(r"^#define (DVD_[A-Z0-9_]+)\s+\(?(-?\d+)\)?\s*(?:/\*.*)?$", text, flags=re.M)}
+    assert defines == rec.constants and len(defines) == n_defines
+    assert (rec.abi is not None) == (f"dvd_{key}_abi_version" in names)
+    if rec.abi:
+        assert rec.abi[0] == f"dvd_{key}_abi_version" and getattr(loaded, rec.abi[0])() == rec.abi[1]
+    # a table line without a function in the library is refused at load, and the library loads again afterwards
+    try:
+        rec.signatures["dvd_no_such_entry"] = "i p"
+        L._handles.pop(key, None)
+        with pytest.raises(RuntimeError, match=f"{rec.so} exports no dvd_no_such_entry -- lib.py and include/{rec.header} disagree"):
+            L._load(key)
+        assert key not in L._handles
+    finally:
+        del rec.signatures["dvd_no_such_entry"]
+        L._handles.pop(key, None)
+        assert L._load(key) is L._handles[key]
+
+
+def test_libraries_know_nothing_of_one_another():
+    """Over every ordered pair of lib.LIBRARIES, the core library included: no entry point of one table is in the other's, no
+    constant of one is among the other's, and the loaded other has no such function.  A side library also owns its prefix,
+    dvd_<key>* and DVD_<KEY>_*, in every other table (dvd_adv_loss of the core library is older than the adv library)."""
+    import itertools
+    from dvd_gan_amd import lib as L
+    assert list(L.LIBRARIES) == ["core"] + list(SIDE_LIBRARIES)
+    for a, b in itertools.permutations(L.LIBRARIES, 2):
+        mine, other = L.LIBRARIES[a], L.LIBRARIES[b]
+        assert not set(mine.signatures) & set(other.signatures), (a, b)
+        assert not set(mine.constants) & set(other.constants), (a, b)
+        assert not [n for n in mine.signatures if hasattr(L._load(b), n)], (a, b)
+        if a != "core":
+            assert [n for n in other.signatures if n.startswith("dvd_" + a)] == (["dvd_adv_loss"] if (a, b) == ("adv", "core") else []), (a, b)
+            assert not [n for n in other.constants if n.startswith("DVD_" + a.upper() + "_")], (a, b)
+
+
+def test_library_table_names_the_directories_and_headers():
+    """lib.LIBRARIES, the *.hip-holding sub-directories of csrc/ (csrc/build.sh makes a library of each) and the dvdgan_hip_*.h
+    files under include/ name the same set, and the module-level names call sites use are views of the table."""
+    import glob
+    from dvd_gan_amd import lib as L
+    csrc = os.path.join(ROOT, "dvd_gan_amd", "csrc")
+    dirs = {os.path.basename(os.path.dirname(f)) for f in glob.glob(os.path.join(csrc, "*", "*.hip"))}
+    headers = {os.path.basename(f)[len("dvdgan_hip_"):-2] for f in glob.glob(os.path.join(ROOT, "include", "dvdgan_hip_*.h"))}
+    assert dirs == headers == set(L.LIBRARIES) - {"core"} and dirs
+    assert glob.glob(os.path.join(csrc, "*.hip")) and os.path.exists(HEADER)
+    for key, rec in L.LIBRARIES.items():
+        suffix, pre = ("", "") if key == "core" else ("_" + key, key.upper() + "_")
+        assert (rec.so, rec.header, rec.env) == (f"libdvdgan_hip{suffix}.so", f"dvdgan_hip{suffix}.h", f"DVD_{pre}LIB_PATH"), key
+        assert getattr(L, pre + "SIGNATURES") is rec.signatures and getattr(L, pre + "HEADER_CONSTANTS") is rec.constants, key
+        assert getattr(L, pre + "LIB_PATH") == L.library_path(key) == (os.environ.get(rec.env) or os.path.join(csrc, rec.so)), key
+        assert getattr(L, pre.lower() + "lib")() is L._load(key) is L._handles[key], key
+        assert rec.abi is None or rec.abi[1] == getattr(L, pre + "ABI_VERSION"), key
+        assert (rec.strerror is None) == (key == "adv") and (rec.strerror is None or rec.strerror in rec.signatures), key
+        if rec.strerror:
+            with pytest.raises(RuntimeError, match=rf"^libdvdgan_hip{suffix}: .* \(code -1\)$"):
+                getattr(L, pre.lower() + "check")(-1)
+
+
+def test_load_all_refuses_a_missing_library(monkeypatch):
+    """What __graft_entry__.build() ends with: every library of the table is loaded, so a missing one (here libdvdgan_hip_geom.so,
+    by its path override, which is read at load time) is an error there."""
+    from dvd_gan_amd import lib as L
+    assert L.load_all() == [L._load(key) for key in L.LIBRARIES]
+    monkeypatch.setenv("DVD_GEOM_LIB_PATH", "/nonexistent/libdvdgan_hip_geom.so")
+    monkeypatch.delitem(L._handles, "geom")
+    with pytest.raises(RuntimeError, match="/nonexistent/libdvdgan_hip_geom.so is missing: build it with .*no CPU / eager fallback"):
+        L.load_all()
 
 
 def test_long_long_arguments_survive_as_plain_ints():
@@ -458,8 +570,8 @@ def test_attention_refusal_rules_need_no_gpu():
 
 def test_missing_library_fails_loudly(monkeypatch):
     from dvd_gan_amd import lib as L
-    monkeypatch.setattr(L, "_lib", None)
-    monkeypatch.setattr(L, "LIB_PATH", "/nonexistent/libdvdgan_hip.so")
+    monkeypatch.delitem(L._handles, "core", raising=False)
+    monkeypatch.setenv("DVD_LIB_PATH", "/nonexistent/libdvdgan_hip.so")
     with pytest.raises(RuntimeError, match="no CPU / eager fallback"):
         L.lib()
 

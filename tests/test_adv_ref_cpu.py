@@ -110,45 +110,6 @@ def test_keep_schedule():
         assert ks[0] == B and ks == sorted(ks, reverse=True) and ks[-1] == max(1, math.ceil(0.3 * B))
 
 
-def test_second_library_handshake():
-    """libdvdgan_hip_adv.so against include/dvdgan_hip_adv.h, the three checks tests/test_abi_cpu.py makes of the core library, with its
-    parser: the library exports exactly the header's declarations, lib.ADV_SIGNATURES says what the prototypes say, and
-    lib.ADV_HEADER_CONSTANTS holds every #define of the header by name and value.  The core library knows nothing of the entry."""
-    import os
-    import re
-    import shutil
-    import subprocess
-    from test_abi_cpu import ROOT, declared_signatures
-    from dvd_gan_amd import lib as L
-    header = os.path.join(ROOT, "include", "dvdgan_hip_adv.h")
-    want = declared_signatures(header)
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    assert sorted(want) == sorted(set(re.findall(r"\b(dvd_[a-z0-9_]+)\s*\(", src))) == ["dvd_adv_loss_ex"]
-    assert {n: sig.replace(" ", "") for n, sig in L.ADV_SIGNATURES.items()} == want
-    adv = L.adv_lib()
-    for name, sig in L.ADV_SIGNATURES.items():
-        fn, sig = getattr(adv, name), sig.replace(" ", "")
-        assert fn.restype is L._CTYPES[sig[0]] and list(fn.argtypes) == [L._CTYPES[c] for c in sig[1:]], name
-    if shutil.which("nm"):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", L.ADV_LIB_PATH]).decode()
-        exported = sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1] not in ("_init", "_fini"))
-        assert exported == sorted(want), exported
-    defines = {n: int(v) for n, v in re.findall(r"^#define (DVD_[A-Z0-9_]+)\s+\(?(-?\d+)\)?\s*(?:/\*.*)?$", open(header).read(), flags=re.M)}
-    assert defines == L.ADV_HEADER_CONSTANTS and len(defines) == 10
-    assert "dvd_adv_loss_ex" not in L.SIGNATURES and not any(n.startswith("DVD_ADV_") for n in L.HEADER_CONSTANTS)
-    assert not hasattr(L.lib(), "dvd_adv_loss_ex")
-    # a table line without a function in the library is refused at load
-    try:
-        L.ADV_SIGNATURES["dvd_no_such_entry"] = "i p"
-        L._adv_lib = None
-        with pytest.raises(RuntimeError, match="exports no dvd_no_such_entry"):
-            L.adv_lib()
-    finally:
-        del L.ADV_SIGNATURES["dvd_no_such_entry"]
-        L._adv_lib = None
-        L.adv_lib()
-
-
 def test_entry_point_is_declared_and_refuses_bad_arguments():
     """dvd_adv_loss_ex: typed from lib.ADV_SIGNATURES, its constants are the header's, and the refusals come back as codes before
     any launch (the placeholder pointers are never dereferenced)."""

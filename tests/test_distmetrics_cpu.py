@@ -1,11 +1,9 @@
-"""Distribution distances without a GPU: the third library's handshake and its refusals (which come back before anything
+"""Distribution distances without a GPU: the eval library's refusals (which come back before anything
 touches the device), the host half of the Frechet distance against closed forms, the subset drawing of kid() and the fp64
 restatement of MMD^2 the GPU tests compare with (tests/distmetrics_ref.py) against a hand computation."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,46 +13,8 @@ import distmetrics_ref as R
 E_ARG, E_SHAPE = -1, -2
 
 
-def test_third_library_handshake():
-    """libdvdgan_hip_eval.so against include/dvdgan_hip_eval.h, the checks tests/test_abi_cpu.py makes of the core library, with its
-    parser: the library exports exactly the header's declarations, lib.EVAL_SIGNATURES says what the prototypes say,
-    lib.EVAL_HEADER_CONSTANTS holds every #define by name and value, and the other two libraries know nothing of it."""
-    from test_abi_cpu import ROOT, declared_signatures
-    from dvd_gan_amd import lib as L
-    header = os.path.join(ROOT, "include", "dvdgan_hip_eval.h")
-    want = declared_signatures(header)
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    assert sorted(want) == sorted(set(re.findall(r"\b(dvd_[a-z0-9_]+)\s*\(", src))) == sorted(
-        ["dvd_eval_strerror", "dvd_eval_pool_features", "dvd_eval_moments_state_doubles", "dvd_eval_moments_update",
-         "dvd_eval_kid_ws_doubles", "dvd_eval_kid"])
-    assert {n: sig.replace(" ", "") for n, sig in L.EVAL_SIGNATURES.items()} == want
-    ev = L.eval_lib()
-    for name, sig in L.EVAL_SIGNATURES.items():
-        fn, sig = getattr(ev, name), sig.replace(" ", "")
-        assert fn.restype is L._CTYPES[sig[0]] and list(fn.argtypes) == [L._CTYPES[c] for c in sig[1:]], name
-    if shutil.which("nm"):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", L.EVAL_LIB_PATH]).decode()
-        exported = sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1] not in ("_init", "_fini"))
-        assert exported == sorted(want), exported
-    defines = {n: int(v) for n, v in re.findall(r"^#define (DVD_[A-Z0-9_]+)\s+\(?(-?\d+)\)?\s*(?:/\*.*)?$", open(header).read(), flags=re.M)}
-    assert defines == L.EVAL_HEADER_CONSTANTS and len(defines) == 3
-    assert not any(n.startswith("dvd_eval") for n in list(L.SIGNATURES) + list(L.ADV_SIGNATURES))
-    assert not any(n.startswith("DVD_EVAL_") for n in list(L.HEADER_CONSTANTS) + list(L.ADV_HEADER_CONSTANTS))
-    assert not hasattr(L.lib(), "dvd_eval_kid") and not hasattr(L.adv_lib(), "dvd_eval_kid")
-    # a table line without a function in the library is refused at load
-    try:
-        L.EVAL_SIGNATURES["dvd_no_such_entry"] = "i p"
-        L._eval_lib = None
-        with pytest.raises(RuntimeError, match="exports no dvd_no_such_entry"):
-            L.eval_lib()
-    finally:
-        del L.EVAL_SIGNATURES["dvd_no_such_entry"]
-        L._eval_lib = None
-        L.eval_lib()
-
-
 def test_resource_file_shows_no_scratch():
-    """csrc/build.sh keeps hipcc's resource remarks of the third library: every kernel of it runs from registers."""
+    """csrc/build.sh keeps hipcc's resource remarks of the eval library: every kernel of it runs from registers."""
     from test_abi_cpu import ROOT
     res = os.path.join(ROOT, "dvd_gan_amd", "csrc", "eval", "build", "distmetrics.res")
     text = open(res).read()

@@ -1,10 +1,8 @@
-"""Precision / recall / density / coverage without a GPU: the fourth library's handshake and its refusals (which come back before
+"""Precision / recall / density / coverage without a GPU: the prdc library's refusals (which come back before
 anything touches the device), its resource file, the fp64 restatement the GPU tests compare with (tests/prdc_ref.py) against a
 hand computation, the GPU tests' cases (decided by their brackets) and the argument checks of distmetrics.prdc()."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,47 +13,8 @@ E_ARG, E_SHAPE = -1, -2
 P_ = 64          # a non-null placeholder pointer: the refusals come before anything is dereferenced
 
 
-def test_fourth_library_handshake():
-    """libdvdgan_hip_prdc.so against include/dvdgan_hip_prdc.h, the checks tests/test_abi_cpu.py makes of the core library, with its
-    parser: the library exports exactly the header's declarations, lib.PRDC_SIGNATURES says what the prototypes say,
-    lib.PRDC_HEADER_CONSTANTS holds every #define by name and value, and the other three libraries know nothing of it."""
-    from test_abi_cpu import ROOT, declared_signatures
-    from dvd_gan_amd import lib as L
-    header = os.path.join(ROOT, "include", "dvdgan_hip_prdc.h")
-    want = declared_signatures(header)
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    assert sorted(want) == sorted(set(re.findall(r"\b(dvd_[a-z0-9_]+)\s*\(", src))) == sorted(
-        ["dvd_prdc_strerror", "dvd_prdc_column_mean", "dvd_prdc_knn_ws_doubles", "dvd_prdc_knn_radii",
-         "dvd_prdc_ball_ws_doubles", "dvd_prdc_ball_count"])
-    assert {n: sig.replace(" ", "") for n, sig in L.PRDC_SIGNATURES.items()} == want
-    pr = L.prdc_lib()
-    for name, sig in L.PRDC_SIGNATURES.items():
-        fn, sig = getattr(pr, name), sig.replace(" ", "")
-        assert fn.restype is L._CTYPES[sig[0]] and list(fn.argtypes) == [L._CTYPES[c] for c in sig[1:]], name
-    if shutil.which("nm"):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", L.PRDC_LIB_PATH]).decode()
-        exported = sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1] not in ("_init", "_fini"))
-        assert exported == sorted(want), exported
-    defines = {n: int(v) for n, v in re.findall(r"^#define (DVD_[A-Z0-9_]+)\s+\(?(-?\d+)\)?\s*(?:/\*.*)?$", open(header).read(), flags=re.M)}
-    assert defines == L.PRDC_HEADER_CONSTANTS and len(defines) == 4
-    others = list(L.SIGNATURES) + list(L.ADV_SIGNATURES) + list(L.EVAL_SIGNATURES)
-    assert not any(n.startswith("dvd_prdc") for n in others)
-    assert not any(n.startswith("DVD_PRDC_") for n in list(L.HEADER_CONSTANTS) + list(L.ADV_HEADER_CONSTANTS) + list(L.EVAL_HEADER_CONSTANTS))
-    assert not any(hasattr(lib, "dvd_prdc_knn_radii") for lib in (L.lib(), L.adv_lib(), L.eval_lib()))
-    # a table line without a function in the library is refused at load
-    try:
-        L.PRDC_SIGNATURES["dvd_no_such_entry"] = "i p"
-        L._prdc_lib = None
-        with pytest.raises(RuntimeError, match="exports no dvd_no_such_entry"):
-            L.prdc_lib()
-    finally:
-        del L.PRDC_SIGNATURES["dvd_no_such_entry"]
-        L._prdc_lib = None
-        L.prdc_lib()
-
-
 def test_resource_file_shows_no_scratch():
-    """csrc/build.sh keeps hipcc's resource remarks of the fourth library: every kernel of it runs from registers -- the sorted
+    """csrc/build.sh keeps hipcc's resource remarks of the prdc library: every kernel of it runs from registers -- the sorted
     neighbour lists (a dynamically indexed per-thread array would live in scratch memory) included, at every capacity."""
     from test_abi_cpu import ROOT
     text = open(os.path.join(ROOT, "dvd_gan_amd", "csrc", "prdc", "build", "prdc.res")).read()

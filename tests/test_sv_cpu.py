@@ -1,12 +1,10 @@
 """Singular-value monitoring without a GPU: the fp64 restatement the GPU tests compare with (tests/sv_ref.py) against the fp64 SVD,
-the seventh library's handshake, its refusals (which come back before anything touches the device), its resource file, the
+the sv library's item mirror, its refusals (which come back before anything touches the device), its resource file, the
 Trainer's settings and the start blocks' private generator."""
 import argparse
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -163,37 +161,15 @@ def test_monitor_refuses_bad_settings():
         top_singular_values([torch.zeros(2, 2)], iters=0)
 
 
-# ------------------------------------------------------------------ the seventh library
-NAMES = ["dvd_sv_abi_version", "dvd_sv_item_size", "dvd_sv_strerror", "dvd_sv_prepare", "dvd_sv_init", "dvd_sv_iterate",
-         "dvd_sv_ritz"]
-
-
-def test_seventh_library_handshake():
-    """libdvdgan_hip_sv.so against include/dvdgan_hip_sv.h, the checks tests/test_abi_cpu.py makes of the core library, with its
-    parser: the library exports exactly the header's declarations, lib.SV_SIGNATURES says what the prototypes say,
-    lib.SV_HEADER_CONSTANTS holds every #define by name and value, the item's mirror has the struct's fields, and the other six
-    libraries know nothing of it."""
-    from test_abi_cpu import ROOT, declared_signatures
+# ------------------------------------------------------------------ the sv library (its handshake: tests/test_abi_cpu.py)
+def test_item_mirror_has_the_struct_s_fields():
+    """lib.SvItem against `dvd_sv_item` of include/dvdgan_hip_sv.h: the size the library was compiled with, and the fields in order
+    with matching kinds.  The sweep limit is the restatement's."""
+    from test_abi_cpu import ROOT
     from dvd_gan_amd import lib as L
-    header = os.path.join(ROOT, "include", "dvdgan_hip_sv.h")
-    text = open(header).read()
-    want = declared_signatures(header)
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert sorted(want) == sorted(set(re.findall(r"\b(dvd_[a-z0-9_]+)\s*\(", src))) == sorted(NAMES)
-    assert {n: sig.replace(" ", "") for n, sig in L.SV_SIGNATURES.items()} == want
-    sv = L.sv_lib()
-    for name, sig in L.SV_SIGNATURES.items():
-        fn, sig = getattr(sv, name), sig.replace(" ", "")
-        assert fn.restype is L._CTYPES[sig[0]] and list(fn.argtypes) == [L._CTYPES[c] for c in sig[1:]], name
-    if shutil.which("nm"):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", L.SV_LIB_PATH]).decode()
-        exported = sorted(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1] not in ("_init", "_fini"))
-        assert exported == sorted(want), exported
-    defines = {n: int(v) for n, v in re.findall(r"^#define (DVD_[A-Z0-9_]+)\s+\(?(-?\d+)\)?\s*(?:/\*.*)?$", text, flags=re.M)}
-    assert defines == L.SV_HEADER_CONSTANTS and len(defines) == 5
-    assert sv.dvd_sv_abi_version() == L.SV_ABI_VERSION and sv.dvd_sv_item_size() == C.sizeof(L.SvItem)
+    assert L.sv_lib().dvd_sv_item_size() == C.sizeof(L.SvItem)
     assert L.SV_MAX_SWEEPS == R.MAX_SWEEPS
-    # the mirror's fields are the struct's, in order, with matching kinds
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dvdgan_hip_sv.h")).read(), flags=re.S)
     body = re.search(r"typedef struct dvd_sv_item \{(.*?)\} dvd_sv_item;", src, flags=re.S).group(1)
     fields = []
     for decl in body.split(";"):
@@ -204,28 +180,10 @@ def test_seventh_library_handshake():
         fields += [(n.strip().lstrip("*"), kind) for n in re.sub(r"^(const\s+)?(float|double|long long|int)\s*\*?", "", decl).split(",")]
     kinds = {C.c_void_p: "p", C.c_longlong: "l", C.c_int: "i"}
     assert fields == [(n, kinds[t]) for n, t in L.SvItem._fields_]
-    others = (list(L.SIGNATURES) + list(L.ADV_SIGNATURES) + list(L.EVAL_SIGNATURES) + list(L.PRDC_SIGNATURES)
-              + list(L.AUG_SIGNATURES) + list(L.GEOM_SIGNATURES))
-    assert not any(n.startswith("dvd_sv_") for n in others)
-    assert not any(n.startswith("DVD_SV_") for n in list(L.HEADER_CONSTANTS) + list(L.ADV_HEADER_CONSTANTS)
-                   + list(L.EVAL_HEADER_CONSTANTS) + list(L.PRDC_HEADER_CONSTANTS) + list(L.AUG_HEADER_CONSTANTS)
-                   + list(L.GEOM_HEADER_CONSTANTS))
-    for other in (L.lib(), L.adv_lib(), L.eval_lib(), L.prdc_lib(), L.aug_lib(), L.geom_lib()):
-        assert not any(hasattr(other, n) for n in NAMES)
-    # a table line without a function in the library is refused at load
-    try:
-        L.SV_SIGNATURES["dvd_no_such_entry"] = "i p"
-        L._sv_lib = None
-        with pytest.raises(RuntimeError, match="exports no dvd_no_such_entry"):
-            L.sv_lib()
-    finally:
-        del L.SV_SIGNATURES["dvd_no_such_entry"]
-        L._sv_lib = None
-        L.sv_lib()
 
 
 def test_resource_file_shows_no_scratch_and_no_spills():
-    """csrc/build.sh keeps hipcc's resource remarks of the seventh library: the four kernels, in both stored widths (the product
+    """csrc/build.sh keeps hipcc's resource remarks of the sv library: the four kernels, in both stored widths (the product
     kernel also in the finish's form), run without scratch memory and without spills."""
     from test_abi_cpu import ROOT
     text = open(os.path.join(ROOT, "dvd_gan_amd", "csrc", "sv", "build", "spectrum.res")).read()
