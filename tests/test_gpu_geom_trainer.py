@@ -66,12 +66,12 @@ def _watch(tr):
             return _orig(*a, **kw)
         net.forward = forward
     tr.G.register_forward_hook(lambda m, a, out: seen["G"].append(out.detach().clone()))
-    for name in ("_aug_table", "_geom_table"):
-        def table(draws, key, *a, _orig=getattr(tr, name)):
-            out = _orig(draws, key, *a)
-            seen["tables"].append((key, out.detach().cpu().clone()))
-            return out
-        setattr(tr, name, table)
+    def tables(*a, _orig=tr._d_tables):                      # the four tables of a D iteration, None for a stage that is off
+        out = _orig(*a)
+        seen["tables"] += [(key, tab.detach().cpu().clone())
+                           for key, tab in zip(("aug_real", "aug_fake", "geom_real", "geom_fake"), out) if tab is not None]
+        return out
+    tr._d_tables = tables
     return seen
 
 

@@ -1,6 +1,7 @@
 """Sample sheets (dvd_gan_amd.sheets, kernel dvd_sample_sheet), the part that needs no GPU: the restatement the GPU tests compare
 the kernel with (checked here against Pillow's paste), the PNG / APNG writers (decoded by Pillow, every CRC walked), the writer
-thread on host tensors, the geometry query, every refusal of the C entry point, and Trainer.fixed_inputs."""
+thread on host tensors, the geometry query, every refusal of the C entry point, and Trainer.fixed_inputs.  The bare config of that
+last part also serves the two tests of the Trainer's settings table (settings.py) and of its no-trace block (`_g_eval`)."""
 import argparse
 import binascii
 import ctypes as C
@@ -387,3 +388,96 @@ def test_trainer_sample_configuration_is_checked():
             Trainer([], _cfg(**bad), device=torch.device("cpu"), compute_dtype=torch.float32)
     tr = Trainer([], _cfg(sample_path="/s", version="v7", sample_epoch=2), device=torch.device("cpu"), compute_dtype=torch.float32)
     assert tr.sample_path == os.path.join("/s", "v7") and tr.sample_epoch == 2 and tr.sample_layout == "frames"
+
+
+# ------------------------------------------------------------------ Trainer on the CPU: the settings table and the no-trace block
+def _cpu_trainer(**extra):
+    from dvd_gan_amd.train_step import Trainer
+    return Trainer([], _cfg(**extra), device=torch.device("cpu"), compute_dtype=torch.float32)
+
+
+# a second valid value for every row's config field (resume and pretrained_model exclude one another: two Trainers)
+SECOND = dict(n_cond=4, g_self_attn=True, g_sep_attn=True, ema_decay=0.5, ema_start=3, ema_standing_stats=2, ema_stats_seed=9,
+              g_ortho=1e-3, g_clip_norm=2.0, d_clip_norm=3.0, skip_nonfinite=True, grad_log=5, lecam=0.25, lecam_decay=0.5,
+              lecam_start=2, g_topk=0.5, g_topk_decay=0.75, d_stats=True, d_aug="cutout,color", d_aug_geom="rotate,xflip",
+              d_aug_p=0.25, d_aug_target=0.5, d_aug_interval=2, d_aug_kimg=100, d_aug_seed=4, sv_log=7, sv_iters=2, sv_log_rows=16,
+              sv_k=2, sv_block=4, sv_seed=5, lr_decay=0.5, model_save_epoch=3, log_epoch=0, state_save_step=10, state_keep=3,
+              sample_step=20, sample_epoch=2, test_batch_size=4, sample_layout="both", sample_fps=12, sample_use_ema=True,
+              sample_seed=6)
+
+
+def test_settings_table_gives_the_constructor_and_the_class_their_defaults(tmp_path):
+    from dvd_gan_amd import settings as S
+    from dvd_gan_amd.train_step import Trainer
+    fields = [row[1] for row in S.SETTINGS]
+    assert len(set(fields)) == len(fields) == len({row[0] for row in S.SETTINGS})
+    assert ("_d_stats_on", "d_stats") in [row[:2] for row in S.SETTINGS]
+    assert set(SECOND) | {"resume", "pretrained_model"} == set(fields)                 # every row is exercised below
+    tr, bare = _cpu_trainer(), Trainer.__new__(Trainer)
+    for attr, field, cast, default in S.SETTINGS:
+        want = cast(default)
+        assert getattr(tr, attr) == want and type(getattr(tr, attr)) is type(want), attr
+        assert getattr(Trainer, attr) == want and type(getattr(Trainer, attr)) is type(want), attr
+        assert getattr(bare, attr) == want, attr                                       # a Trainer that never ran __init__
+    assert S.DEFAULTS == {attr: getattr(Trainer, attr) for attr, *_ in S.SETTINGS}
+    assert tr.d_aug == () and tr.d_aug_geom == () and tr.resume is None and tr.sample_epoch == 0 and tr.d_aug_p == 1.0
+    for name, want in (("_adv_ex", False), ("_adv_stats", None), ("_anchors", None), ("_ema_block", False), ("_epoch", 0),
+                       ("_labels_registered", None), ("_sheets", None), ("_state_writer", None), ("g_optimizer", None)):
+        assert getattr(bare, name) is want or getattr(bare, name) == want, name        # the run state that used to be guarded
+    # a second valid value of every field reaches its attribute, through the row's cast
+    other = _cpu_trainer(model_save_path=str(tmp_path), version="", **SECOND)
+    by_field = {row[1]: row for row in S.SETTINGS}
+    for field, value in SECOND.items():
+        attr, _, cast, default = by_field[field]
+        assert getattr(other, attr) == cast(value) != cast(default), field
+    assert other.d_aug == ("color", "cutout") and other.d_aug_geom == ("xflip", "rotate") and other._d_stats_on is True
+    assert other.fingerprint()["g_self_attn"] is True and hasattr(other.G, "self_attn") and hasattr(other.G, "sep_attn")
+    other.save_models(5)                                                               # pretrained_model needs its files
+    loaded = _cpu_trainer(model_save_path=str(tmp_path), version="", pretrained_model=5, **SECOND)
+    assert loaded.pretrained_model == 5
+    assert all(torch.equal(a, b) for a, b in zip(loaded.G.state_dict().values(), other.G.state_dict().values()))
+    assert _cpu_trainer(resume="latest").resume == "latest" and _cpu_trainer(resume="").resume is None
+    assert getattr(Trainer, "d_aug_p") == 1.0 and other.d_aug_p == 0.25                # the class keeps the table's default
+
+
+@pytest.mark.parametrize("restore", [True, False])
+def test_no_trace_block_puts_the_generators_frozen_tensors_back(restore):
+    tr = _cpu_trainer()
+    G = tr.G
+    u = next(p.data for n, p in G.named_parameters() if n.endswith("weight_u"))
+    mean = next(b for n, b in G.named_buffers() if n.endswith("running_mean"))
+    count = next(b for n, b in G.named_buffers() if n.endswith("num_batches_tracked"))
+    assert not next(p for n, p in G.named_parameters() if n.endswith("weight_u")).requires_grad
+    mean.copy_(torch.randn(mean.shape))
+    count.fill_(3)
+    watched = (u, mean, count)
+    before = [t.clone() for t in watched]
+    everything = [t.clone() for t in tr._g_frozen_tensors()]
+
+    def overwrite():
+        u.add_(1.5)
+        mean.mul_(2.0).add_(1.0)
+        count.add_(4)
+        assert not any(torch.equal(t, old) for t, old in zip(watched, before))
+
+    class Boom(Exception):
+        pass
+
+    assert G.training
+    with pytest.raises(Boom):
+        with tr._g_eval(restore=restore) as put_back:
+            assert not G.training
+            overwrite()
+            dirty = [t.clone() for t in watched]
+            put_back()
+            for t, old, d in zip(watched, before, dirty):
+                assert torch.equal(t, old if restore else d)
+            if restore:
+                overwrite()
+            raise Boom()
+    assert G.training                                                                  # back in train mode either way
+    if restore:
+        assert all(torch.equal(t, old) for t, old in zip(watched, before))
+        assert all(torch.equal(t, old) for t, old in zip(tr._g_frozen_tensors(), everything))
+    else:
+        assert all(torch.equal(t, d) for t, d in zip(watched, dirty))                  # quirk 2: what the passes left stays
