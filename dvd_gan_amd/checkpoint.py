@@ -10,7 +10,8 @@ A state file is one dict of CPU tensors and plain Python scalars / lists / strin
     tensors         name -> tensor: "net.<G|Ds|Dt>.<state_dict key>" for every entry that is not a trained weight (spectral-norm
                     u / v, batch-norm running statistics and counters), "opt.<G|Ds|Dt>.<flat|m|v|ema>" (the trained weights ARE
                     `flat`, in parameter order), "opt.<..>.<guard_state|guard_ring|ortho_penalty>"
-    host            everything kept on the host: step counts, learning rates, schedulers, epoch, loader position, random streams
+    host            everything kept on the host: step counts, learning rates, schedulers, epoch, loader position, random streams,
+                    and "params": per network the trained tensors' names and shapes in `flat`'s order (parameter_table)
 There is no arithmetic here and no kernel: the snapshot is copies on streams, pinned memory and events.
 """
 import os
@@ -63,6 +64,30 @@ def check_fingerprint(saved, mine):
         if saved.get(k) != mine[k]:
             raise ValueError(f"{k}: the state was written with {k}={saved.get(k)!r}, this Trainer has {k}={mine[k]!r} (a state "
                              "continues only the configuration that wrote it)")
+
+
+def parameter_table(net):
+    """[[name, shape], ...] of a network's trained tensors, in the order the optimizer's `flat` holds them."""
+    return [[k, [int(d) for d in p.shape]] for k, p in net.named_parameters() if p.requires_grad]
+
+
+def check_parameters(tag, saved, net):
+    """ValueError naming the first trained tensor of `net` the file lacks or holds in another shape (or the first one the file
+    holds and the network lacks): two architectures whose fingerprints agree -- a ConvGRU and a TSRU generator -- differ here.
+    saved: the file's parameter_table of this network, or None (a file from before the table: the optimizer's element count is
+    the only check then)."""
+    if saved is None:
+        return
+    held = {k: list(shape) for k, shape in saved}
+    mine = parameter_table(net)
+    for k, shape in mine:
+        if held.get(k) != shape:
+            raise ValueError(f"net.{tag}.{k}: the state holds {None if k not in held else tuple(held[k])}, the network "
+                             f"{tuple(shape)}")
+    names = {k for k, _ in mine}
+    for k, shape in saved:
+        if k not in names:
+            raise ValueError(f"net.{tag}.{k}: the state holds {tuple(shape)}, the network has no such tensor")
 
 
 def latest_state(folder):

@@ -3,6 +3,8 @@
 # By convention: the *.hip files here make the core library libdvdgan_hip.so (include/dvdgan_hip.h), and every sub-directory
 # <dir> that holds *.hip files makes a library of its own, libdvdgan_hip_<dir>.so with the header include/dvdgan_hip_<dir>.h
 # (its objects stay out of build/*.o).  dvd_gan_amd/lib.py's LIBRARIES has one entry for each.
+# The extension family beside it: every ../xsrc/<key>/ that holds *.hip files makes ../xsrc/libdvdx_<key>.so with the header
+# include/dvdx_<key>.h (lib.py's EXTENSIONS) -- same flags, same .res files, same out-of-date rule; csrc/common.h may be included.
 # Every compile also leaves build/<file>.res = hipcc's kernel-resource-usage remarks (registers, spills, scratch per kernel):
 # tests/test_abi_cpu.py holds the hot kernels to "no scratch" with it (a dynamically indexed accumulator array once put every
 # convolution kernel's accumulators into scratch memory: 3x on the step, invisible to every parity test).
@@ -35,10 +37,19 @@ for d in */; do
 done
 compile_dir "" dvdgan_hip.h
 for d in "${dirs[@]}"; do compile_dir "$d/" "dvdgan_hip_$d.h"; done
+xdirs=()
+for d in ../xsrc/*/; do
+  if compgen -G "$d*.hip" > /dev/null; then xdirs+=("$(basename "$d")"); fi
+done
+for d in "${xdirs[@]}"; do compile_dir "../xsrc/$d/" "dvdx_$d.h"; done
 for p in "${pids[@]}"; do wait "$p"; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o libdvdgan_hip.so build/*.o
 echo "built $(pwd)/libdvdgan_hip.so"
 for d in "${dirs[@]}"; do
   hipcc --offload-arch=gfx950 -shared -fPIC -o "libdvdgan_hip_$d.so" "$d"/build/*.o
   echo "built $(pwd)/libdvdgan_hip_$d.so"
+done
+for d in "${xdirs[@]}"; do
+  hipcc --offload-arch=gfx950 -shared -fPIC -o "../xsrc/libdvdx_$d.so" "../xsrc/$d"/build/*.o
+  echo "built $(cd ../xsrc && pwd)/libdvdx_$d.so"
 done

@@ -1025,3 +1025,178 @@ class GatherFrames(Function):
         Lr = g[0, 0].numel()
         out = K.row_copy(g.contiguous().view(-1, Lr), rows, B * T, Lr, scatter=True)
         return out.view(ctx.shape), None
+
+
+# ------------------------------------------------------------------ TSRU layer (libdvdx_tsru.so)
+# Test aid, forward only: the flow head is not run and the unit is fed a zero flow, so the warped state IS h_{t-1}.  A forward
+# pass made under it refuses its backward pass (the flow head's gradients would belong to a head that never ran).
+TSRU_BYPASS_WARP = False
+
+
+def tsru_flow_channels(hidden):
+    """F of the flow gate: max(8, hidden / 4) rounded up to a multiple of 8."""
+    return K.pad8(max(8, -(-hidden // 4)))
+
+
+def tsru_forward(h_prev, a, off_c, off_u, theta_raw, d, h, h_c):
+    """One launch of dvdx_tsru_forward: h [B,S1,S2,C] fp32 (and its copy h_c in a's dtype, or None) from the fp32 state h_prev, the
+    pre-activations a [B,S1,S2,lda] (a_c at column off_c, a_u at off_u) and the raw flow theta_raw [B,S1,S2,ldt] fp32."""
+    B, S1, S2, Cc = h_prev.shape
+    L.tsru_check(L.tsru_lib().dvdx_tsru_forward(L.dt(a), L.ptr(h_prev), L.ptr(a), a.shape[-1], off_c, off_u, L.ptr(theta_raw),
+                                                theta_raw.shape[-1], d, L.ptr(h), L.ptr(h_c), B, S1, S2, Cc, L.stream()))
+    return h
+
+
+def tsru_backward(dh, dh2, h_prev, a, off_c, off_u, theta_raw, d, da, doff_c, doff_u, dtheta_raw, addend, dh_prev, ws):
+    """The two launches of dvdx_tsru_backward (include/dvdx_tsru.h); ws: B*S1*S2*(C+2) floats."""
+    B, S1, S2, Cc = h_prev.shape
+    assert ws.numel() >= B * S1 * S2 * (Cc + 2)
+    L.tsru_check(L.tsru_lib().dvdx_tsru_backward(
+        L.dt(a), L.ptr(dh), L.ptr(dh2), L.ptr(h_prev), L.ptr(a), a.shape[-1], off_c, off_u, L.ptr(theta_raw), theta_raw.shape[-1], d,
+        L.ptr(da), da.shape[-1], doff_c, doff_u, L.ptr(dtheta_raw), dtheta_raw.shape[-1], L.ptr(addend), L.ptr(dh_prev), L.ptr(ws),
+        B, S1, S2, Cc, L.stream()))
+    return dh_prev
+
+
+def _tsru_packs(wc, wu, wf, wo, dtype, dev):
+    """The five packs of a layer: x-part and h-part of [out | update] and of the flow gate, and the 3 x 3 flow head."""
+    hid, ctot, k = wc.shape[0], wc.shape[1], wc.shape[-1]
+    cin, F_ = ctot - hid, wf.shape[0]
+    pxg = K.PackedConv(dtype, 2 * hid, cin, (k, k), dev, covered=True)
+    phg = K.PackedConv(dtype, 2 * hid, hid, (k, k), dev, covered=True)
+    for g, w in enumerate((wc, wu)):
+        pxg.fill(w, co_off=g * hid, ci_off=0)
+        phg.fill(w, co_off=g * hid, ci_off=cin)
+    pxf = K.PackedConv(dtype, F_, cin, (k, k), dev, single_fill=True).fill(wf, ci_off=0)
+    phf = K.PackedConv(dtype, F_, hid, (k, k), dev, single_fill=True).fill(wf, ci_off=cin)
+    po = K.PackedConv(dtype, 2, F_, (3, 3), dev, single_fill=True).fill(wo)
+    return pxg, phg, pxf, phf, po
+
+
+class ConvTSRULayer(Function):
+    """All T steps of one TSRUCell (gen_net.py): [a_c | a_u | a_f] = W * [x ; h_{t-1}] + b, theta = d tanh(W_o * relu(a_f) + b_o),
+    h_t = u warp(h_{t-1}, theta) + (1 - u) relu(a_c).  x: [T*B,S,S,Cin_p] t-major frames, or [B,S,S,Cin_p] when the same input
+    feeds every step.  Returns h of every step as [T*B,S,S,hidden] in x's dtype; the state itself is carried in fp32.
+    The x-part of the gate convolutions is batched over all T steps; on the serial chain a step is two recurrent convolutions
+    ([out | update] and the flow gate, each adding its x-part as the residual), the flow head and one dvdx_tsru_forward launch.
+    The backward pass walks the chain back: dvdx_tsru_backward (gate gradients, flow gradient, transpose of the warp plus the
+    upstream gradient of step t-1), the flow head's and the two recurrent backward-data convolutions; everything else -- input
+    gradient, all weight gradients -- is batched over T afterwards."""
+
+    @staticmethod
+    def forward(ctx, x, wc, bc, wu, bu, wf, bf, wo, bo, T, shared_x, h0, d, infer=False):
+        dev, dtype = x.device, x.dtype
+        hid, ctot, k = wc.shape[0], wc.shape[1], wc.shape[-1]
+        cin, F_ = ctot - hid, wf.shape[0]
+        B = x.shape[0] if shared_x else x.shape[0] // T
+        S1, S2 = x.shape[1], x.shape[2]
+        f32 = dtype == torch.float32
+        packs = _tsru_packs(wc, wu, wf, wo, dtype, dev)
+        pxg, phg, pxf, phf, po = packs
+        gxg = K.conv_forward(x, pxg.wf, (k, k), 2 * hid, bias=torch.cat([bc, bu]), wq=lambda: pxg.fragment_major("wf"))
+        gxf = K.conv_forward(x, pxf.wf, (k, k), F_, bias=bf, wq=lambda: pxf.fragment_major("wf"))
+        n = 2 if infer else T                     # inference keeps two steps of everything but the output sequence
+        mk = lambda c, dt_=dtype, steps=n: torch.empty(steps, B, S1, S2, c, dtype=dt_, device=dev)
+        h_all = mk(hid, steps=T)                  # the layer's output; in exact mode also the fp32 states
+        h32 = h_all if f32 else mk(hid, torch.float32)
+        ag, af, th = mk(2 * hid), mk(F_), mk(8, torch.float32)
+        if TSRU_BYPASS_WARP:
+            th.zero_()
+        if h0 is None:
+            h0_32 = torch.zeros(B, S1, S2, hid, dtype=torch.float32, device=dev)
+        else:
+            h0_32 = h0 if f32 else K.convert(h0, torch.float32)
+        step = lambda t_: slice(None) if shared_x else slice(t_ * B, (t_ + 1) * B)
+        for t in range(T):
+            i = t % n
+            hp32 = h0_32 if t == 0 else h32[(t - 1) % (T if f32 else n)]
+            hpc = h0 if t == 0 else h_all[t - 1]
+            if hpc is None:                       # a zero state: the recurrent convolutions add nothing
+                ag[i].copy_(gxg[step(t)])
+                af[i].copy_(gxf[step(t)])
+            else:
+                K.conv_forward(hpc, phg.wf, (k, k), 2 * hid, res=gxg[step(t)], out=ag[i], wq=lambda: phg.fragment_major("wf"))
+                K.conv_forward(hpc, phf.wf, (k, k), F_, res=gxf[step(t)], out=af[i], wq=lambda: phf.fragment_major("wf"))
+            if not TSRU_BYPASS_WARP:
+                K.conv_forward(af[i], po.wf, (3, 3), 2, bias=bo, relu_in=True, out=th[i], out_f32=True)
+            tsru_forward(hp32, ag[i], 0, hid, th[i], d, h32[t if f32 else i], None if f32 else h_all[t])
+        out = h_all.view(T * B, S1, S2, hid)
+        if infer:
+            return out
+        ctx.save_for_backward(x, wc, wu, wf, wo, h_all, h32, ag, af, th, h0, h0_32)
+        ctx.params = (wc, bc, wu, bu, wf, bf, wo, bo)
+        ctx.packs = packs
+        ctx.meta = (T, B, S1, S2, hid, cin, F_, k, shared_x, d)
+        ctx.bypassed = TSRU_BYPASS_WARP
+        return out
+
+    @staticmethod
+    def backward(ctx, dh_out):
+        x, wc, wu, wf, wo, h_all, h32, ag, af, th, h0, h0_32 = ctx.saved_tensors
+        pxg, phg, pxf, phf, po = ctx.packs
+        T, B, S1, S2, hid, cin, F_, k, shared_x, d = ctx.meta
+        if ctx.bypassed:
+            raise RuntimeError("ConvTSRULayer: the forward pass ran under TSRU_BYPASS_WARP (a forward-only test aid): no backward")
+        dev, dtype = x.device, x.dtype
+        f32 = dtype == torch.float32
+        M = B * S1 * S2
+        dh_out = dh_out.contiguous()
+        up32 = (dh_out if f32 else K.convert(dh_out, torch.float32)).view(T, B, S1, S2, hid)      # upstream gradient of every step
+        dgg = torch.empty(T * B, S1, S2, 2 * hid, dtype=dtype, device=dev)
+        dgf = torch.empty(T * B, S1, S2, F_, dtype=dtype, device=dev)
+        dth = torch.zeros(T * B, S1, S2, 8, dtype=dtype, device=dev)                               # columns 2..7 stay zero
+        ws = torch.empty(M * (hid + 2), dtype=torch.float32, device=dev)
+        carry = [torch.empty(B, S1, S2, hid, dtype=torch.float32, device=dev) for _ in range(2)]
+        want_dh0 = h0 is not None and ctx.needs_input_grad[11]
+        dh, dh2 = up32[T - 1], None               # the state's gradient of step t is dh + dh2
+        for t in range(T - 1, -1, -1):
+            rows = slice(t * B, (t + 1) * B)
+            hp32 = h0_32 if t == 0 else h32[t - 1]
+            nxt = carry[t & 1]
+            tsru_backward(dh, dh2, hp32, ag[t], 0, hid, th[t], d, dgg[rows], 0, hid, dth[rows], up32[t - 1] if t else None, nxt, ws)
+            K.conv_forward(dth[rows], po.wd, (3, 3), po.cip, mask=af[t], out=dgf[rows])
+            if t == 0 and not want_dh0:
+                break
+            part = K.conv_forward(dgg[rows], phg.wd, (k, k), phg.cip, wq=lambda: phg.fragment_major("wd"))
+            dh2 = K.conv_forward(dgf[rows], phf.wd, (k, k), phf.cip, res=part, out_f32=True, wq=lambda: phf.fragment_major("wd"))
+            dh = nxt
+        dh0 = None
+        if want_dh0:
+            dh0 = K.add(dh, dh2)
+            dh0 = dh0 if h0.dtype == torch.float32 else K.convert(dh0, h0.dtype)
+        # ---- everything below is batched over all T steps ----
+        if shared_x:
+            dgxg = K.sum_leading(dgg.view(T, -1)).view(B, S1, S2, 2 * hid)
+            dgxf = K.sum_leading(dgf.view(T, -1)).view(B, S1, S2, F_)
+        else:
+            dgxg, dgxf = dgg, dgf
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.conv_forward(dgxg, pxg.wd, (k, k), pxg.cip, wq=lambda: pxg.fragment_major("wd"))
+            dx = K.conv_forward(dgxf, pxf.wd, (k, k), pxf.cip, res=dx, wq=lambda: pxf.fragment_major("wd"))
+        params = ctx.params
+        hflat = h_all.view(T * B, S1, S2, hid)
+        afl = af.view(T * B, S1, S2, F_)
+
+        def wgrads(dws, dbs):
+            """dws / dbs: fp32 buffers (reference layouts) of out, update, flow gate and flow head, ACCUMULATED into"""
+            for i, (dgx, dg, col, cout) in enumerate(((dgxg, dgg, 0, hid), (dgxg, dgg, hid, hid), (dgxf, dgf, 0, F_))):
+                K.conv_wgrad(x, dgx, dws[i], (k, k), cout, cin, dy_col=col, dw_ci_off=0, dw_ci_tot=cin + hid, dbias=dbs[i])
+                if h0 is not None:
+                    K.conv_wgrad(h0, dg, dws[i], (k, k), cout, hid, dy_col=col, dw_ci_off=cin, dw_ci_tot=cin + hid, frames=B,
+                                 x_row0=0, dy_row0=0)
+                if T > 1:
+                    K.conv_wgrad(hflat, dg, dws[i], (k, k), cout, hid, dy_col=col, dw_ci_off=cin, dw_ci_tot=cin + hid,
+                                 frames=(T - 1) * B, x_row0=0, dy_row0=B)
+            K.conv_wgrad(afl, dth, dws[3], (3, 3), 2, F_, relu_in=True, dbias=dbs[3])
+
+        if _direct(*params):
+            _side_run(lambda: wgrads([p.grad for p in params[0::2]], [p.grad for p in params[1::2]]), x, dgxg, dgxf, dgg, dgf, dth,
+                      h_all, af, h0)
+            gr = [None] * 8
+        else:
+            dws = [torch.zeros_like(w) for w in (wc, wu, wf, wo)]
+            dbs = [torch.zeros(w.shape[0], dtype=torch.float32, device=dev) for w in (wc, wu, wf, wo)]
+            wgrads(dws, dbs)
+            gr = [v for pair in zip(dws, dbs) for v in pair]
+        return (dx, *gr, None, None, dh0, None, None)

@@ -73,6 +73,60 @@ class ConvGRU(nn.Module):
         return outs
 
 
+class TSRUCell(nn.Module):
+    """Parameter holder of one TSRU_p layer (Luc et al. 2020; the reference has none), keys in the ConvGRU's style:
+    {update,out,flow}_gate.{weight,bias} over [x ; h] with the ConvGRU layer's kernel size, and flow_out.{weight,bias}, the 3 x 3
+    head from the F = Fn.tsru_flow_channels(hidden) flow features to the (x, y) flow.  No reset gate.  flow_out starts at zero:
+    the flow is zero, the warped state is h_{t-1} itself, and the unit is a ConvGRU without a reset gate."""
+
+    def __init__(self, input_size, hidden_size, kernel_size, flow):
+        super().__init__()
+        self.input_size, self.hidden_size, self.kernel_size, self.flow = input_size, hidden_size, kernel_size, float(flow)
+        k = (kernel_size, kernel_size)
+        self.flow_channels = Fn.tsru_flow_channels(hidden_size)
+        self.update_gate = ConvParams(input_size + hidden_size, hidden_size, k, "orthogonal")
+        self.out_gate = ConvParams(input_size + hidden_size, hidden_size, k, "orthogonal")
+        self.flow_gate = ConvParams(input_size + hidden_size, self.flow_channels, k, "orthogonal")
+        self.flow_out = ConvParams(self.flow_channels, 2, (3, 3), "zero")
+
+    def run(self, x, T, shared_x, h0=None):
+        return Fn.ConvTSRULayer.apply(x, self.out_gate.weight, self.out_gate.bias, self.update_gate.weight, self.update_gate.bias,
+                                      self.flow_gate.weight, self.flow_gate.bias, self.flow_out.weight, self.flow_out.bias,
+                                      T, shared_x, h0, self.flow, not torch.is_grad_enabled())
+
+
+class ConvTSRU(nn.Module):
+    """A stack of TSRU layers with ConvGRU's constructor (plus the flow range in pixels) and ConvGRU's `run` contract: layer l
+    over the whole sequence, then layer l+1.  No wavefront over the layers."""
+
+    def __init__(self, input_size, hidden_sizes, kernel_sizes, n_layers, flow=2.0):
+        super().__init__()
+        if not isinstance(hidden_sizes, list):
+            hidden_sizes = [hidden_sizes] * n_layers
+        if not isinstance(kernel_sizes, list):
+            kernel_sizes = [kernel_sizes] * n_layers
+        assert len(hidden_sizes) == n_layers, "`hidden_sizes` must have the same length as n_layers"
+        assert len(kernel_sizes) == n_layers, "`kernel_sizes` must have the same length as n_layers"
+        check_tsru_flow(flow)
+        self.input_size, self.hidden_sizes, self.kernel_sizes, self.n_layers = input_size, hidden_sizes, kernel_sizes, n_layers
+        self.cells = nn.ModuleList(
+            TSRUCell(input_size if i == 0 else hidden_sizes[i - 1], hidden_sizes[i], kernel_sizes[i], flow)
+            for i in range(n_layers))
+
+    def run(self, x, T, shared_x, hidden=None):
+        """x: [T*B,S,S,C] t-major (or [B,S,S,C] if shared_x).  Returns the list of per-layer sequences [T*B,S,S,h_l]."""
+        outs = []
+        for i, cell in enumerate(self.cells):
+            x = cell.run(x, T, shared_x and i == 0, None if hidden is None else hidden[i])
+            outs.append(x)
+        return outs
+
+
+def check_tsru_flow(flow):
+    if not 0 < flow <= L.TSRU_MAX_FLOW:           # (a NaN fails too)
+        raise ValueError(f"tsru_flow={flow}: the flow range must lie in (0, {L.TSRU_MAX_FLOW}] pixels")
+
+
 class GResBlock(nn.Module):
     """GResBlock.py:9-86 with bn=True, downsample_factor=1 (the only configuration the generator uses)."""
 
@@ -108,12 +162,17 @@ class Generator(nn.Module):
     .forward(z [B,in_dim] f32, class_id [B] i64) -> [B, T, 3, 16*latent_dim, 16*latent_dim] f32."""
 
     def __init__(self, in_dim=120, latent_dim=4, n_class=4, ch=32, n_frames=48, hierar_flag=False,
-                 compute_dtype=torch.bfloat16, self_attn=False, sep_attn=False, n_cond=0):
+                 compute_dtype=torch.bfloat16, self_attn=False, sep_attn=False, n_cond=0, rnn="gru", tsru_flow=2.0):
         """self_attn / sep_attn switch on the two attention blocks the reference defines and imports (Generator.py:10) but
         leaves commented out: `self.self_attn = SelfAttention(8 * ch)` (:29) over the (T, ld, ld) latent clip after the first
         ConvGRU, and `SeparableAttn(4 * ch)` (:34, after the block that produces 4*ch channels) over the (T, 8 ld, 8 ld) clip
-        after module 8.  Parameter keys: `self_attn.*`, `sep_attn.model.{0,1,2}.*` (absent when off: reference checkpoints load)."""
+        after module 8.  Parameter keys: `self_attn.*`, `sep_attn.model.{0,1,2}.*` (absent when off: reference checkpoints load).
+        rnn: "gru" (the reference's ConvGRU) or "tsru" (the TSRU_p of Luc et al. 2020 in every recurrent stack, same hidden and
+        kernel sizes; tsru_flow = the flow range d in pixels of each layer's own grid)."""
         super().__init__()
+        if rnn not in ("gru", "tsru"):
+            raise ValueError(f"rnn={rnn!r}: the recurrent unit is 'gru' or 'tsru'")
+        check_tsru_flow(tsru_flow)
         if hierar_flag:
             raise NotImplementedError("hierar_flag=True is broken in the reference (Generator.py:66,109)")
         if ch < 2 or ch % 2:
@@ -132,14 +191,16 @@ class Generator(nn.Module):
         self.affine_transfrom = nn.Linear(in_dim * 2, latent_dim * latent_dim * 8 * ch)
         c8, c4, c2 = 8 * ch, 4 * ch, 2 * ch
         nc = in_dim * 2
+        self.rnn, self.tsru_flow = rnn, float(tsru_flow)
+        RNN = ConvGRU if rnn == "gru" else (lambda *a: ConvTSRU(*a, flow=tsru_flow))
         self.conv = nn.ModuleList([
-            ConvGRU(c8, [c8, 2 * c8, c8], [3, 5, 3], 3),
+            RNN(c8, [c8, 2 * c8, c8], [3, 5, 3], 3),
             GResBlock(c8, c8, nc, 1), GResBlock(c8, c8, nc),
-            ConvGRU(c8, [c8, 2 * c8, c8], [3, 5, 3], 3),
+            RNN(c8, [c8, 2 * c8, c8], [3, 5, 3], 3),
             GResBlock(c8, c8, nc, 1), GResBlock(c8, c8, nc),
-            ConvGRU(c8, [c8, 2 * c8, c8], [3, 5, 3], 3),
+            RNN(c8, [c8, 2 * c8, c8], [3, 5, 3], 3),
             GResBlock(c8, c8, nc, 1), GResBlock(c8, c4, nc),
-            ConvGRU(c4, [c4, 2 * c4, c4], [3, 5, 5], 3),
+            RNN(c4, [c4, 2 * c4, c4], [3, 5, 5], 3),
             GResBlock(c4, c4, nc, 1), GResBlock(c4, c2, nc),
         ])
         self.colorize = SpectralNormConv(c2, 3, (3, 3))
@@ -163,7 +224,9 @@ class Generator(nn.Module):
         every ConditionalNorm.embed.weight -- the reference's initialisation (sn_layers.py:212-213) sets the first C columns of
         every row to about 1 and the rest to 0, so its rows are nearly equal by design and the penalty would fight it."""
         from .sn_layers import ConditionalNorm
-        return [self.embedding.weight] + [m.embed.weight for m in self.modules() if isinstance(m, ConditionalNorm)]
+        # (a TSRU's flow head starts at zero and must stay free to grow in whatever direction the flow needs)
+        return ([self.embedding.weight] + [m.embed.weight for m in self.modules() if isinstance(m, ConditionalNorm)]
+                + [m.flow_out.weight for m in self.modules() if isinstance(m, TSRUCell)])
 
     def forward(self, x, class_id, hidden=None, cond=None):
         """hidden (frame-conditional variant, BASELINE configs[4]): initial ConvGRU states supplied by the caller -- one entry
@@ -227,7 +290,7 @@ class Generator(nn.Module):
             samp = ((b_glob * T + t_idx) % cond.shape[0]).reshape(-1).to(torch.int32)
         n_gru = 0
         for k, m in enumerate(self.conv):
-            if isinstance(m, ConvGRU):
+            if isinstance(m, (ConvGRU, ConvTSRU)):
                 h0 = hidden[n_gru] if hidden is not None else None
                 n_gru += 1
                 if h0 is not None and not states_cl:

@@ -1,5 +1,5 @@
 """ctypes binding of the shared libraries csrc/build.sh makes, one per header under include/: LIBRARIES (at the end) is the table of
-them, _load() the one handshake.  Fails loudly: no fallback."""
+them, EXTENSIONS the table of the second family (xsrc/), _load() the one handshake of both.  Fails loudly: no fallback."""
 import ctypes as C
 import os
 from typing import NamedTuple
@@ -238,6 +238,19 @@ SV_SIGNATURES = {
     "dvd_sv_ritz": "i ppii i ppp ll p",
 }
 
+# ---- The extension family (xsrc/<key>/*.hip -> xsrc/libdvdx_<key>.so, include/dvdx_<key>.h, EXTENSIONS below): same records, same
+# handshake.  libdvdx_tsru.so (include/dvdx_tsru.h): warp-and-gate kernels of the TSRU recurrent unit (functional.ConvTSRULayer)
+TSRU_ABI_VERSION = 1
+TSRU_MAX_FLOW, TSRU_MAX_SIDE, TSRU_THREADS = 8, 1024, 256
+TSRU_HEADER_CONSTANTS = {"DVDX_" + name: value for name, value in list(globals().items())
+                         if name.startswith("TSRU_") and isinstance(value, int)}
+TSRU_SIGNATURES = {
+    "dvdx_tsru_abi_version": "i",
+    "dvdx_tsru_strerror": "s i",
+    "dvdx_tsru_forward": "i i pp iii pi f pp iiii p",
+    "dvdx_tsru_backward": "i i pppp iii pi f p iii pi ppp iiii p",
+}
+
 
 class SvItem(C.Structure):              # == dvd_sv_item
     _fields_ = [("W", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("state_off", C.c_longlong), ("ws_off", C.c_longlong),
@@ -376,20 +389,39 @@ LIBRARIES = {
     "sv": _library("sv", SV_SIGNATURES, SV_HEADER_CONSTANTS, abi=("dvd_sv_abi_version", SV_ABI_VERSION), strerror="dvd_sv_strerror",
                    structs=lambda so: [("sizeof(dvd_sv_item)", so.dvd_sv_item_size(), SvItem)]),
 }
+
+
+def _extension(key, signatures, constants, **handshake):
+    return Library(f"libdvdx_{key}.so", f"DVDX_{key.upper()}_LIB_PATH", f"dvdx_{key}.h", signatures, constants, **handshake)
+
+
+# The second family, beside the first because tests/test_abi_cpu.py fixes the first one's set of libraries, directories and headers:
+# a directory xsrc/<key>/ of .hip files, include/dvdx_<key>.h and one entry here.
+EXTENSIONS = {
+    "tsru": _extension("tsru", TSRU_SIGNATURES, TSRU_HEADER_CONSTANTS, abi=("dvdx_tsru_abi_version", TSRU_ABI_VERSION),
+                       strerror="dvdx_tsru_strerror"),
+}
+assert not set(LIBRARIES) & set(EXTENSIONS)
 _handles = {}           # key -> checked handle; _handles.pop(key, None) drops one, and the next accessor call loads it again
 
 
+def _record(key):
+    """The Library record of a key of either table."""
+    return LIBRARIES[key] if key in LIBRARIES else EXTENSIONS[key]
+
+
 def library_path(key):
-    """Where LIBRARIES[key] is loaded from: its environment variable, read now, or csrc/ of this tree."""
-    return os.environ.get(LIBRARIES[key].env) or os.path.join(_HERE, "csrc", LIBRARIES[key].so)
+    """Where the library of `key` is loaded from: its environment variable, read now, or csrc/ (xsrc/ for an extension) of this tree."""
+    rec = _record(key)
+    return os.environ.get(rec.env) or os.path.join(_HERE, "csrc" if key in LIBRARIES else "xsrc", rec.so)
 
 
 def _load(key):
-    """The loaded LIBRARIES[key].  The first call dlopens it and runs its whole handshake; the handle is published only after
+    """The loaded library of LIBRARIES[key] / EXTENSIONS[key].  The first call dlopens it and runs its whole handshake; the handle is published only after
     every check has passed.  Raises (never falls back) when the library has not been built or disagrees with this file."""
     if key in _handles:
         return _handles[key]
-    rec, path = LIBRARIES[key], library_path(key)
+    rec, path = _record(key), library_path(key)
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(dvd_gan_amd has no CPU / eager fallback)")
@@ -417,8 +449,13 @@ def load_all():
     return [_load(key) for key in LIBRARIES]
 
 
+def load_extensions():
+    """Every library of the extension table, loaded and checked (__graft_entry__.build() calls it after load_all())."""
+    return [_load(key) for key in EXTENSIONS]
+
+
 def _fail(key, code):
-    rec = LIBRARIES[key]
+    rec = _record(key)
     raise RuntimeError(f"{rec.so[:-3]}: {getattr(_load(key), rec.strerror)(code).decode()} (code {code})")
 
 
@@ -435,7 +472,7 @@ def _accessor(key):
             return _handles[key]
         except KeyError:
             return _load(key)
-    handle.__doc__ = f"The loaded {LIBRARIES[key].so}, typed from its signature table.  Raises (never falls back) when it has not been built."
+    handle.__doc__ = f"The loaded {_record(key).so}, typed from its signature table.  Raises (never falls back) when it has not been built."
     return handle
 
 
@@ -452,6 +489,8 @@ prdc_check = _checker("prdc")
 aug_check = _checker("aug")
 geom_check = _checker("geom")
 sv_check = _checker("sv")
+tsru_lib = _accessor("tsru")
+tsru_check = _checker("tsru")
 
 
 # the paths as this import found them (tools and tests that inspect the files)

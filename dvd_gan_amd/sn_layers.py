@@ -36,6 +36,9 @@ class ConvParams(nn.Module):
         if init == "orthogonal":            # ConvGRU.py:20-26
             nn.init.orthogonal_(self.weight)
             nn.init.zeros_(self.bias)
+        elif init == "zero":                # a head that starts as the zero map (gen_net.TSRUCell.flow_out)
+            nn.init.zeros_(self.weight)
+            nn.init.zeros_(self.bias)
         elif init == "xavier":              # Discriminators.py:73-76
             nn.init.xavier_uniform_(self.weight)
             nn.init.zeros_(self.bias)

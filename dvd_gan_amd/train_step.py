@@ -174,12 +174,20 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
     _state_writer = None          # the checkpoint.StateWriter, made at the first save_state()
     g_optimizer = None
 
-    def __init__(self, data_loader, config, device=None, compute_dtype=torch.bfloat16, latent_dim=4, dp_mode="replica"):
+    def __init__(self, data_loader, config, device=None, compute_dtype=torch.bfloat16, latent_dim=4, dp_mode="replica", rnn="gru",
+                 tsru_flow=2.0):
         """dp_mode (data-parallel runs only): "replica" = per-replica batch-norm statistics and condition rows, the
         semantics of the reference's nn.DataParallel (trainer.py:353-359); "global" = cross-replica conditional batch
-        norm + gathered conditions: N ranks reproduce one process on the global batch."""
+        norm + gathered conditions: N ranks reproduce one process on the global batch.
+        rnn, tsru_flow: the generator's recurrent unit and its flow range (gen_net.Generator); an architecture choice like
+        latent_dim, so a keyword here and no config field."""
         if dp_mode not in ("replica", "global"):
             raise ValueError("dp_mode must be 'replica' or 'global'")
+        if rnn not in ("gru", "tsru"):
+            raise ValueError(f"rnn={rnn!r}: the recurrent unit is 'gru' or 'tsru'")
+        from .gen_net import check_tsru_flow
+        check_tsru_flow(tsru_flow)
+        self.rnn, self.tsru_flow = rnn, float(tsru_flow)
         self.dp_mode = dp_mode
         self.data_loader = data_loader
         c = self.config = config
@@ -372,7 +380,8 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
     def build_model(self):
         dt = self.compute_dtype
         self.G = Generator(self.z_dim, self.latent_dim, self.n_class, self.g_chn, self.n_frames, compute_dtype=dt,
-                           self_attn=self.g_self_attn, sep_attn=self.g_sep_attn, n_cond=self.n_cond).to(self.device)
+                           self_attn=self.g_self_attn, sep_attn=self.g_sep_attn, n_cond=self.n_cond, rnn=self.rnn,
+                           tsru_flow=self.tsru_flow).to(self.device)
         self.D_s = SpatialDiscriminator(self.ds_chn, self.n_class, compute_dtype=dt).to(self.device)
         self.D_t = TemporalDiscriminator(self.dt_chn, self.n_class, compute_dtype=dt).to(self.device)
         if self.exchange.active and self.dp_mode == "global":

@@ -91,7 +91,8 @@ class TrainerReports(object):
         for tag, mon in mons.items():
             sv, res, fro2, sn = (t.tolist() for t in mon.split(mon.ring[self.sv_log_rows].cpu()))
             out[tag] = [{"name": n, "shape": tuple(t.shape), "sv": sv[i], "res": res[i],
-                         "stable_rank": fro2[i] / sv[i][0] ** 2 if sv[i][0] > 0.0 else float("nan"),
+                         # (an all-zero matrix -- a TSRU's flow head at initialisation -- has rank 0, not an undefined one)
+                         "stable_rank": fro2[i] / sv[i][0] ** 2 if sv[i][0] > 0.0 else 0.0 if fro2[i] == 0.0 else float("nan"),
                          "sn_sigma": sn[i] if mon.sn[i] is not None else None}
                         for i, (n, t) in enumerate(zip(mon.names, mon.tensors))]
         return out

@@ -78,6 +78,7 @@ class TrainerState(object):
                 "loader": own["loader"], "frame_gen": None if self.frame_gen is None else self.frame_gen.get_state().clone()}
         if "aug" in own:
             host["aug"] = own["aug"]
+        host["params"] = {tag: C.parameter_table(net) for tag, net in self._nets()}
         items, slabs = [], {}
         copy_of = lambda t: (lambda dst: dst.copy_(t))
         for tag, net in self._nets():
@@ -128,12 +129,15 @@ class TrainerState(object):
         sets the optimizers' t / lr, the schedules, step and epoch, the loader's position (when the loader has
         load_state_dict()) and the host random streams.  Read with weights_only=True.  ValueError naming the field on an
         unknown format_version, on the first fingerprint field that differs, and on a tensor that is missing or of another
-        shape.  In a data-parallel run every rank reads this file and its own `{step}_state.rank{r}.pt` next to it.  -> list of
+        shape (trained ones included: a ConvGRU generator's state is refused by a TSRU generator, and vice versa, by name).
+        In a data-parallel run every rank reads this file and its own `{step}_state.rank{r}.pt` next to it.  -> list of
         warning strings (settings that only steer future steps and differ from the file's; the constructor's hold)."""
         from . import checkpoint as C
         sd = C.load_file(path)
         C.check_fingerprint(sd["fingerprint"], self.fingerprint())
         tensors, host, step = sd["tensors"], sd["host"], int(sd["step"])
+        for tag, net in self._nets():       # the trained tensors by name and shape, before anything is copied
+            C.check_parameters(tag, host.get("params", {}).get(tag), net)
         own = host
         if D.world_size() > 1:
             rank_file = C.state_path(os.path.dirname(path), step, self.rank)
