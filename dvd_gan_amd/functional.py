@@ -967,6 +967,30 @@ class AdvLossEx(Function):
         return dout * g, None, None, None, None, None, None, None
 
 
+class CRLoss(Function):
+    """weight * mean((aug - clean)^2) of a discriminator's logits of transformed clips and of the same clips untransformed
+    (balanced consistency regularization, Zhao et al. 2020; dvdx_cr_pair, one launch; libdvdx_cr.so) -> scalar.
+    stats: None or a float32 [lib.CR_NSTAT] device view, overwritten.  Both gradients come from the forward launch, as AdvLoss's
+    does.  Nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, aug, clean, weight, stats):
+        if aug.shape != clean.shape:
+            raise ValueError(f"CRLoss: logits of {tuple(aug.shape)} transformed and {tuple(clean.shape)} clean views")
+        aug, clean = aug.contiguous(), clean.contiguous()
+        loss = torch.zeros(1, dtype=torch.float32, device=aug.device)
+        d_aug, d_clean = torch.empty_like(aug), torch.empty_like(clean)
+        L.cr_check(L.cr_lib().dvdx_cr_pair(L.ptr(aug), L.ptr(clean), aug.numel(), float(weight), L.ptr(loss), L.ptr(d_aug),
+                                           L.ptr(d_clean), L.ptr(stats), L.stream()))
+        ctx.save_for_backward(d_aug, d_clean)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        d_aug, d_clean = ctx.saved_tensors
+        return d_aug * g, d_clean * g, None, None
+
+
 # ------------------------------------------------------------------ reference-layout helpers
 class VidDownsample(Function):
     """utils.py:77-83"""

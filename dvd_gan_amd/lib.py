@@ -1,5 +1,6 @@
 """ctypes binding of the shared libraries csrc/build.sh makes, one per header under include/: LIBRARIES (at the end) is the table of
-them, EXTENSIONS the table of the second family (xsrc/), _load() the one handshake of both.  Fails loudly: no fallback."""
+them, EXTENSIONS and MORE_EXTENSIONS the tables of the second family (xsrc/), _load() the one handshake of all.  Fails loudly: no
+fallback."""
 import ctypes as C
 import os
 from typing import NamedTuple
@@ -251,6 +252,19 @@ TSRU_SIGNATURES = {
     "dvdx_tsru_backward": "i i pppp iii pi f p iii pi ppp iiii p",
 }
 
+# libdvdx_cr.so (include/dvdx_cr.h, MORE_EXTENSIONS below): the pair loss of balanced consistency regularization on a
+# discriminator's logits, its two gradients and its statistics row (functional.CRLoss)
+CR_ABI_VERSION = 1
+CR_MAX_N, CR_THREADS, CR_NSTAT = 1 << 20, 256, 5
+(CR_STAT_PENALTY, CR_STAT_MSQ, CR_STAT_MAXABS, CR_STAT_NONZERO, CR_STAT_N) = range(CR_NSTAT)
+CR_HEADER_CONSTANTS = {"DVDX_" + name: value for name, value in list(globals().items())
+                       if name.startswith("CR_") and isinstance(value, int)}
+CR_SIGNATURES = {
+    "dvdx_cr_abi_version": "i",
+    "dvdx_cr_strerror": "s i",
+    "dvdx_cr_pair": "i pp l f ppp p p",
+}
+
 
 class SvItem(C.Structure):              # == dvd_sv_item
     _fields_ = [("W", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("state_off", C.c_longlong), ("ws_off", C.c_longlong),
@@ -402,12 +416,21 @@ EXTENSIONS = {
                        strerror="dvdx_tsru_strerror"),
 }
 assert not set(LIBRARIES) & set(EXTENSIONS)
+# The rest of the second family -- same directory (xsrc/), same records, same build loop -- in a table of its own because
+# tests/test_tsru_cpu.py fixes EXTENSIONS to its one key and load_extensions() to its one handle.
+MORE_EXTENSIONS = {
+    "cr": _extension("cr", CR_SIGNATURES, CR_HEADER_CONSTANTS, abi=("dvdx_cr_abi_version", CR_ABI_VERSION), strerror="dvdx_cr_strerror"),
+}
+assert not (set(LIBRARIES) | set(EXTENSIONS)) & set(MORE_EXTENSIONS)
 _handles = {}           # key -> checked handle; _handles.pop(key, None) drops one, and the next accessor call loads it again
 
 
 def _record(key):
-    """The Library record of a key of either table."""
-    return LIBRARIES[key] if key in LIBRARIES else EXTENSIONS[key]
+    """The Library record of a key of any of the three tables."""
+    for table in (LIBRARIES, EXTENSIONS):
+        if key in table:
+            return table[key]
+    return MORE_EXTENSIONS[key]
 
 
 def library_path(key):
@@ -417,7 +440,7 @@ def library_path(key):
 
 
 def _load(key):
-    """The loaded library of LIBRARIES[key] / EXTENSIONS[key].  The first call dlopens it and runs its whole handshake; the handle is published only after
+    """The loaded library of the table row `key`.  The first call dlopens it and runs its whole handshake; the handle is published only after
     every check has passed.  Raises (never falls back) when the library has not been built or disagrees with this file."""
     if key in _handles:
         return _handles[key]
@@ -452,6 +475,11 @@ def load_all():
 def load_extensions():
     """Every library of the extension table, loaded and checked (__graft_entry__.build() calls it after load_all())."""
     return [_load(key) for key in EXTENSIONS]
+
+
+def load_more_extensions():
+    """Every library of MORE_EXTENSIONS, loaded and checked (__graft_entry__.build() calls it after load_extensions())."""
+    return [_load(key) for key in MORE_EXTENSIONS]
 
 
 def _fail(key, code):
@@ -491,6 +519,8 @@ geom_check = _checker("geom")
 sv_check = _checker("sv")
 tsru_lib = _accessor("tsru")
 tsru_check = _checker("tsru")
+cr_lib = _accessor("cr")
+cr_check = _checker("cr")
 
 
 # the paths as this import found them (tools and tests that inspect the files)

@@ -44,6 +44,10 @@ config.d_aug_interval steps (Karras et al. 2020; `d_aug_p` is the current value)
 config.d_aug_geom = "xflip,rot90,scale,rotate,aniso" (any subset) warps the clips before that: ADA's geometric group as one
 affine map per clip, bilinear with zero fill (geom_augment.py: two more HIP launches, the warp and its exact transpose, no
 atomics); it shares d_aug_p and its steering, d_aug_seed and the tables' generator with d_aug, and either works without the other.
+Trainer(..., d_cr=lambda_real, d_cr_fake=lambda_fake) adds balanced consistency regularization (Zhao et al. 2020, "Improved
+Consistency Regularization for GANs") on those same transforms: in a D iteration every discriminator call takes the transformed
+views followed by the clean views of the same clips, and lambda * mean((D(T(x)) - D(x))^2) joins the network's loss (one more
+HIP launch per call, functional.CRLoss; the generator step is untouched); `cr_report()` is the one call that reads its statistics.
 `evaluate_samples(real, n_samples=N, embed=...)` measures generation from noise (n_cond = 0): the Frechet and the kernel distance
 between features of real and of generated clips (distmetrics.py; the statistic of FVD / FID / KID, on the device).  `embed` is the
 caller's feature extractor or "Dt" / "Ds", this Trainer's own discriminator features -- comparable only under ONE fixed
@@ -167,6 +171,9 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
     _adv_ex = False               # a stabiliser or the logit statistics are on: calc_loss takes the AdvLossEx launch
     _adv_stats = None             # fp32 [6][lib.ADV_NSTAT]: D_s real / fake, D_t real / fake, G step D_s / D_t
     _anchors = None               # fp32 [2 slots][D_s, D_t][real, fake] on the device, when lecam > 0
+    d_cr = 0.0                    # weights of the consistency penalty on real / on generated clips (constructor keywords)
+    d_cr_fake = 0.0
+    _cr_stats = None              # fp32 [4][lib.CR_NSTAT]: D_s real / fake, D_t real / fake, when either weight is > 0
     _ema_block = False            # inside ema_weights()
     _epoch = 0                    # epochs train() has started
     _labels_registered = None     # register_label_buffer()'s tensor
@@ -175,18 +182,29 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
     g_optimizer = None
 
     def __init__(self, data_loader, config, device=None, compute_dtype=torch.bfloat16, latent_dim=4, dp_mode="replica", rnn="gru",
-                 tsru_flow=2.0):
+                 tsru_flow=2.0, d_cr=0.0, d_cr_fake=None):
         """dp_mode (data-parallel runs only): "replica" = per-replica batch-norm statistics and condition rows, the
         semantics of the reference's nn.DataParallel (trainer.py:353-359); "global" = cross-replica conditional batch
         norm + gathered conditions: N ranks reproduce one process on the global batch.
         rnn, tsru_flow: the generator's recurrent unit and its flow range (gen_net.Generator); an architecture choice like
-        latent_dim, so a keyword here and no config field."""
+        latent_dim, so a keyword here and no config field.
+        d_cr, d_cr_fake: the weights lambda_real and lambda_fake of balanced consistency regularization (Zhao et al. 2020; the
+        paper uses 10 for both): in a D iteration each discriminator is asked to give a clip and its d_aug / d_aug_geom view the
+        same logit, L_D += d_cr * mean((D(T(x)) - D(x))^2) + d_cr_fake * mean((D(T(G(z))) - D(G(z)))^2).  0 = off; d_cr_fake =
+        None takes d_cr.  They steer future steps only: neither the fingerprint nor the state file knows them.  In a data-parallel
+        run the penalty is a mean over the rank's shard, which the gradient exchange turns into the mean over the global batch
+        when the shards are equal (unverified, like every other stabiliser there)."""
         if dp_mode not in ("replica", "global"):
             raise ValueError("dp_mode must be 'replica' or 'global'")
         if rnn not in ("gru", "tsru"):
             raise ValueError(f"rnn={rnn!r}: the recurrent unit is 'gru' or 'tsru'")
         from .gen_net import check_tsru_flow
         check_tsru_flow(tsru_flow)
+        d_cr = float(d_cr)
+        d_cr_fake = d_cr if d_cr_fake is None else float(d_cr_fake)
+        if not (0.0 <= d_cr < float("inf") and 0.0 <= d_cr_fake < float("inf")):
+            raise ValueError(f"d_cr={d_cr}, d_cr_fake={d_cr_fake}: the consistency weights are finite and >= 0")
+        self.d_cr, self.d_cr_fake = d_cr, d_cr_fake
         self.rnn, self.tsru_flow = rnn, float(tsru_flow)
         self.dp_mode = dp_mode
         self.data_loader = data_loader
@@ -239,6 +257,9 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
                 or not 0.0 < self.d_aug_kimg < float("inf")):
             raise ValueError(f"d_aug_p={self.d_aug_p} (in [0, 1]), d_aug_target={self.d_aug_target} (in [0, 1), 0 = fixed p), "
                              f"d_aug_interval={self.d_aug_interval} (>= 1), d_aug_kimg={self.d_aug_kimg} (finite, > 0)")
+        if (self.d_cr > 0.0 or self.d_cr_fake > 0.0) and not (self.d_aug or self.d_aug_geom):
+            raise ValueError(f"d_cr={self.d_cr}, d_cr_fake={self.d_cr_fake} with d_aug and d_aug_geom both empty: there is no "
+                             "transform for the discriminators to be consistent under")
         self._aug_adaptive = bool(self.d_aug or self.d_aug_geom) and self.d_aug_target > 0.0
         self._aug_gen = None          # the tables' generator, made below once the rank is known
         self._aug_steps = 0           # steps taken with d_aug or d_aug_geom on
@@ -278,7 +299,9 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
             self._adv_stats = torch.zeros(6, L.ADV_NSTAT, dtype=torch.float32, device=self.device)
             if self.lecam > 0.0:
                 self._anchors = torch.zeros(2, 2, 2, dtype=torch.float32, device=self.device)
-        Fn.direct_weight_grads(True)          # weight gradients accumulate into FlatAdam's buffers on a side stream
+        if self.d_cr > 0.0 or self.d_cr_fake > 0.0:
+            self._cr_stats = torch.zeros(4, L.CR_NSTAT, dtype=torch.float32, device=self.device)
+        Fn.direct_weight_grads(True)         # weight gradients accumulate into FlatAdam's buffers on a side stream
         self.exchange = GradExchange()
         # The step's dependent chain runs on a high-priority stream (ahead of the bulk weight-gradient stream) -- in a
         # single-process run.  In a data-parallel run the gradient exchange takes the urgent level instead and the chain
@@ -462,6 +485,17 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
     def _site_loss(self, x, real_flag, site):
         return self.calc_loss(x, real_flag, _site=site) if self._adv_ex else self.calc_loss(x, real_flag)
 
+    def _d_pair(self, net, view, clean, labels, real_flag, site):
+        """One discriminator call of a D iteration with the consistency penalty on -> (adversarial term, penalty).  The
+        transformed views and the clean views of the same clips go through ONE call on a batch twice as long (both networks are
+        per-sample, no batch norm), so the spectral-norm vectors advance once per call as without the penalty.  The first half
+        of the logits is what the call returns today and goes through _site_loss unchanged; the penalty is
+        d_cr / d_cr_fake * mean((first - second)^2) (functional.CRLoss), its statistics row `site` of _cr_stats."""
+        out = net(torch.cat([view, clean]), torch.cat([labels, labels]))
+        n = out.numel() // 2
+        return (self._site_loss(out[:n], real_flag, site),
+                Fn.CRLoss.apply(out[:n], out[n:], self.d_cr if real_flag else self.d_cr_fake, self._cr_stats[site]))
+
     def _end_d_iteration(self):
         """The anchors of the slot this D iteration wrote become those of the global batch (the update is linear in the batch
         mean and the shards are equal): one all-reduce of 4 floats, only in a data-parallel run."""
@@ -549,12 +583,14 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
         fg = self.frame_gen
         draws_all = draws
         aug, geo = bool(self.d_aug), bool(self.d_aug_geom)
+        cr = self._cr_stats is not None
         tab_real = tab_fake = mat_real = mat_fake = None
         for _ in range(self.d_iters):
             if isinstance(draws_all, (list, tuple)):              # test aid: one dict of draws per discriminator iteration
                 draws = draws_all[_]
             ids_real = draw_frame_ids(T, k, fg) if draws is None else torch.as_tensor(draws["perm_real"])[:k].sort()[0]
-            early = self._aux is not None
+            # (with the consistency penalty on, the real passes stay on the chain: the opt-in side-stream path is not taken)
+            early = self._aux is not None and not cr
             real_in = real_videos
             if aug or geo:
                 tab_real, tab_fake, mat_real, mat_fake = self._d_tables(draws, real_videos.shape[0], *real_videos.shape[-2:])
@@ -601,24 +637,42 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
                 cur.wait_stream(self._aux)
                 for t_ in (ds_loss_real, dt_loss_real, real_d):
                     t_.record_stream(cur)
+            elif cr:
+                # balanced consistency regularization: every discriminator call of the D iteration takes [transformed | clean]
+                # views of the same clips (the same frame ids), and the penalties join the network's loss before its one backward
+                ds_loss_real, ds_cr_real = self._d_pair(
+                    self.D_s, real_s, sample_k_frames(real_videos, T + Kc, k, ids_real + Kc if Kc else ids_real), real_labels, True, 0)
             else:
                 ds_loss_real = self._site_loss(self.D_s(real_s, real_labels), True, 0)
-            ds_loss_fake = self._site_loss(self.D_s(fake_s.detach(), z_class), False, 1)
+            if cr:
+                fake_clean = fake_videos.detach()
+                ds_loss_fake, ds_cr_fake = self._d_pair(self.D_s, fake_s.detach(), sample_k_frames(fake_clean, T, k, ids_fake),
+                                                        z_class, False, 1)
+            else:
+                ds_loss_fake = self._site_loss(self.D_s(fake_s.detach(), z_class), False, 1)
             self.reset_grad()
-            (ds_loss_real + ds_loss_fake).backward()
+            (ds_loss_real + ds_loss_fake + ds_cr_real + ds_cr_fake if cr else ds_loss_real + ds_loss_fake).backward()
             Fn.join_side()
             ex.start("Ds", self.ds_optimizer.grad)
             # ---------------- D_t (its forward/backward overlaps the D_s gradient exchange)
             fake_d = vid_downsample(fake_in) if cond is None else vid_downsample_cat(cond_in, fake_in)
-            if not early:
-                real_d = vid_downsample(real_in)
-                dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
-            dt_loss_fake = self._site_loss(self.D_t(fake_d.detach(), z_class), False, 3)
+            if cr:
+                # the clean view of the fake call is [raw context | generated]
+                dt_loss_real, dt_cr_real = self._d_pair(self.D_t, vid_downsample(real_in), vid_downsample(real_videos), real_labels,
+                                                        True, 2)
+                dt_loss_fake, dt_cr_fake = self._d_pair(
+                    self.D_t, fake_d.detach(), vid_downsample(fake_clean) if cond is None else vid_downsample_cat(cond, fake_clean),
+                    z_class, False, 3)
+            else:
+                if not early:
+                    real_d = vid_downsample(real_in)
+                    dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
+                dt_loss_fake = self._site_loss(self.D_t(fake_d.detach(), z_class), False, 3)
             ex.finish("Ds")
             self.ds_optimizer.step()
             self.ds_lr_scher.step((ds_loss_real + ds_loss_fake) if self._plateau else None)
             self.dt_optimizer.zero_grad()
-            (dt_loss_real + dt_loss_fake).backward()
+            (dt_loss_real + dt_loss_fake + dt_cr_real + dt_cr_fake if cr else dt_loss_real + dt_loss_fake).backward()
             Fn.join_side()
             ex.start("Dt", self.dt_optimizer.grad)
             self._end_d_iteration()

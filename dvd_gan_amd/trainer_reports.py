@@ -49,6 +49,18 @@ class TrainerReports(object):
                         "g_kept": int(g[L.ADV_STAT_KEPT]), "g_mean": g[L.ADV_STAT_MEAN]}
         return out
 
+    def cr_report(self):
+        """The consistency penalties of the last D iteration as a host dict, or None when d_cr and d_cr_fake are both 0.  The one
+        call of this group that synchronizes.  Per site (Ds_real, Ds_fake, Dt_real, Dt_fake): the penalty as it entered the
+        network's loss, the mean squared gap between the logits of the transformed and of the clean views, the largest |gap|,
+        the pairs whose gap is not zero, and the number of pairs n."""
+        if self._cr_stats is None:
+            return None
+        s = self._cr_stats.cpu().tolist()
+        return {site: {"penalty": row[L.CR_STAT_PENALTY], "mean_sq_gap": row[L.CR_STAT_MSQ], "max_abs_gap": row[L.CR_STAT_MAXABS],
+                       "nonzero": int(row[L.CR_STAT_NONZERO]), "n": int(row[L.CR_STAT_N])}
+                for site, row in zip(("Ds_real", "Ds_fake", "Dt_real", "Dt_fake"), s)}
+
     # ---- singular values of the weights (spectral.py)
     def _sv_monitors(self):
         """One monitor per network over every trainable tensor with dim() >= 2 (named by its state_dict key), with the layer's
