@@ -4,7 +4,7 @@
 # <dir> that holds *.hip files makes a library of its own, libdvdgan_hip_<dir>.so with the header include/dvdgan_hip_<dir>.h
 # (its objects stay out of build/*.o).  dvd_gan_amd/lib.py's LIBRARIES has one entry for each.
 # The extension family beside it: every ../xsrc/<key>/ that holds *.hip files makes ../xsrc/libdvdx_<key>.so with the header
-# include/dvdx_<key>.h (lib.py's EXTENSIONS and MORE_EXTENSIONS) -- same flags, same .res files, same out-of-date rule; csrc/common.h may be included.
+# include/dvdx_<key>.h (lib.py's EXTENSIONS, MORE_EXTENSIONS and ZCR_EXTENSIONS) -- same flags, same .res files, same out-of-date rule; csrc/common.h may be included.
 # Every compile also leaves build/<file>.res = hipcc's kernel-resource-usage remarks (registers, spills, scratch per kernel):
 # tests/test_abi_cpu.py holds the hot kernels to "no scratch" with it (a dynamically indexed accumulator array once put every
 # convolution kernel's accumulators into scratch memory: 3x on the step, invisible to every parity test).

@@ -991,6 +991,40 @@ class CRLoss(Function):
         return d_aug * g, d_clean * g, None, None
 
 
+class PairDistance(Function):
+    """-weight * mean((both[:P] - both[P:])^2) over the two halves of `both` [2 P, ...] fp32, the generator's clips of the base
+    and of the perturbed latents in ONE tensor as the generator returns them (the generator part of latent consistency
+    regularization, Zhao et al. 2020; dvdx_zcr_dist, libdvdx_zcr.so) -> scalar.  stats: None or a float32 [lib.ZCR_NSTAT] device
+    view, overwritten.  The backward is one more streaming launch (dvdx_zcr_dist_grad) that reads the upstream scalar on the
+    device and writes the [2 P, ...] gradient of `both` in one pass: nothing of full size is kept in between but `both` itself,
+    and autograd pads and adds nothing (two sliced inputs would cost a zero fill, a copy and an add per half).  Nothing is read
+    back."""
+
+    @staticmethod
+    def forward(ctx, both, weight, stats):
+        if both.dtype != torch.float32 or not both.is_contiguous():
+            raise ValueError(f"PairDistance: the halves must be contiguous fp32, got {both.dtype}, contiguous={both.is_contiguous()}")
+        if both.dim() < 2 or both.shape[0] < 2 or both.shape[0] % 2:
+            raise ValueError(f"PairDistance: {tuple(both.shape)} is not [2 * pairs, ...]")
+        pairs = both.shape[0] // 2
+        n = both.numel() // (2 * pairs)
+        ws = torch.empty(K.zcr_ws_doubles(pairs, n), dtype=torch.float64, device=both.device)
+        term = torch.zeros(1, dtype=torch.float32, device=both.device)
+        K.zcr_dist(both[:pairs], both[pairs:], pairs, n, weight, ws, term, stats)
+        ctx.save_for_backward(both)
+        ctx.weight = float(weight)
+        return term.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        both, = ctx.saved_tensors
+        pairs = both.shape[0] // 2
+        grad = torch.empty_like(both)
+        K.zcr_dist_grad(both[:pairs], both[pairs:], pairs, both.numel() // (2 * pairs), ctx.weight,
+                        g.to(torch.float32).contiguous(), grad[:pairs], grad[pairs:])
+        return grad, None, None
+
+
 # ------------------------------------------------------------------ reference-layout helpers
 class VidDownsample(Function):
     """utils.py:77-83"""

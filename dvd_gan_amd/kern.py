@@ -603,6 +603,26 @@ def ortho_grad(p, g, items_host, items_dev, strength, ws, penalty=None):
                                    int(items_host.shape[0]), float(strength), L.ptr(ws), L.ptr(penalty), L.stream()))
 
 
+def zcr_ws_doubles(pairs, n):
+    """Doubles of the workspace zcr_dist needs for fp32 [pairs, n] halves (dvdx_zcr_ws_doubles; 0: a shape it refuses)."""
+    return int(L.zcr_lib().dvdx_zcr_ws_doubles(int(pairs), int(n)))
+
+
+def zcr_dist(a, b, pairs, n, weight, ws, term, stats=None):
+    """term[0] <- -weight * mean((a - b)^2) over the fp32 [pairs, n] halves a, b (views welcome: only their data pointers are
+    taken), stats (None or fp32 [lib.ZCR_NSTAT]) <- the statistics row; ws: float64 [zcr_ws_doubles(pairs, n)].  Two launches."""
+    assert ws.dtype == torch.float64 and term.dtype == torch.float32
+    L.zcr_check(L.zcr_lib().dvdx_zcr_dist(L.ptr(a), L.ptr(b), int(pairs), int(n), float(weight), L.ptr(ws), ws.numel(), L.ptr(term),
+                                          L.ptr(stats), L.stream()))
+
+
+def zcr_dist_grad(a, b, pairs, n, weight, upstream, da, db):
+    """da, db [pairs, n] <- the gradients of upstream[0] * zcr_dist's term; `upstream` is a DEVICE fp32 scalar, never read here."""
+    assert upstream.dtype == torch.float32 and upstream.numel() == 1
+    L.zcr_check(L.zcr_lib().dvdx_zcr_dist_grad(L.ptr(a), L.ptr(b), int(pairs), int(n), float(weight), L.ptr(upstream), L.ptr(da),
+                                               L.ptr(db), L.stream()))
+
+
 def ema_step(ema, p, decay):
     L.check(L.lib().dvd_ema_step(L.ptr(ema), L.ptr(p), p.numel(), float(decay), L.stream()))
 

@@ -1,6 +1,6 @@
 """ctypes binding of the shared libraries csrc/build.sh makes, one per header under include/: LIBRARIES (at the end) is the table of
-them, EXTENSIONS and MORE_EXTENSIONS the tables of the second family (xsrc/), _load() the one handshake of all.  Fails loudly: no
-fallback."""
+them, EXTENSIONS, MORE_EXTENSIONS and ZCR_EXTENSIONS the tables of the second family (xsrc/), _load() the one handshake of all.
+Fails loudly: no fallback."""
 import ctypes as C
 import os
 from typing import NamedTuple
@@ -265,6 +265,22 @@ CR_SIGNATURES = {
     "dvdx_cr_pair": "i pp l f ppp p p",
 }
 
+# libdvdx_zcr.so (include/dvdx_zcr.h, ZCR_EXTENSIONS below): the clip distance of latent consistency regularization between the
+# generator's clips of the base and of the perturbed latents, its statistics row and its gradient (functional.PairDistance)
+ZCR_ABI_VERSION = 1
+ZCR_MAX_PAIRS, ZCR_MAX_N, ZCR_THREADS, ZCR_MAX_BLOCKS, ZCR_MIN_CHUNK, ZCR_NSTAT = 1 << 16, 1 << 40, 256, 2048, 4096, 6
+(ZCR_STAT_TERM, ZCR_STAT_MSQ, ZCR_STAT_MIN_PAIR, ZCR_STAT_MAX_PAIR, ZCR_STAT_MAXABS, ZCR_STAT_PAIRS) = range(ZCR_NSTAT)
+ZCR_HEADER_CONSTANTS = {"DVDX_" + name: value for name, value in list(globals().items())
+                        if name.startswith("ZCR_") and isinstance(value, int)}
+ZCR_SIGNATURES = {
+    "dvdx_zcr_abi_version": "i",
+    "dvdx_zcr_strerror": "s i",
+    "dvdx_zcr_chunks": "l ll",
+    "dvdx_zcr_ws_doubles": "l ll",
+    "dvdx_zcr_dist": "i pp ll f pl pp p",
+    "dvdx_zcr_dist_grad": "i pp ll f p pp p",
+}
+
 
 class SvItem(C.Structure):              # == dvd_sv_item
     _fields_ = [("W", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("state_off", C.c_longlong), ("ws_off", C.c_longlong),
@@ -422,15 +438,22 @@ MORE_EXTENSIONS = {
     "cr": _extension("cr", CR_SIGNATURES, CR_HEADER_CONSTANTS, abi=("dvdx_cr_abi_version", CR_ABI_VERSION), strerror="dvdx_cr_strerror"),
 }
 assert not (set(LIBRARIES) | set(EXTENSIONS)) & set(MORE_EXTENSIONS)
+# ... and a fourth table for the same reason: tests/test_cr_cpu.py fixes MORE_EXTENSIONS to its one key and
+# load_more_extensions() to its one handle.
+ZCR_EXTENSIONS = {
+    "zcr": _extension("zcr", ZCR_SIGNATURES, ZCR_HEADER_CONSTANTS, abi=("dvdx_zcr_abi_version", ZCR_ABI_VERSION),
+                      strerror="dvdx_zcr_strerror"),
+}
+assert not (set(LIBRARIES) | set(EXTENSIONS) | set(MORE_EXTENSIONS)) & set(ZCR_EXTENSIONS)
 _handles = {}           # key -> checked handle; _handles.pop(key, None) drops one, and the next accessor call loads it again
 
 
 def _record(key):
-    """The Library record of a key of any of the three tables."""
-    for table in (LIBRARIES, EXTENSIONS):
+    """The Library record of a key of any of the four tables."""
+    for table in (LIBRARIES, EXTENSIONS, MORE_EXTENSIONS):
         if key in table:
             return table[key]
-    return MORE_EXTENSIONS[key]
+    return ZCR_EXTENSIONS[key]
 
 
 def library_path(key):
@@ -482,6 +505,11 @@ def load_more_extensions():
     return [_load(key) for key in MORE_EXTENSIONS]
 
 
+def load_zcr_extensions():
+    """Every library of ZCR_EXTENSIONS, loaded and checked (__graft_entry__.build() calls it after load_more_extensions())."""
+    return [_load(key) for key in ZCR_EXTENSIONS]
+
+
 def _fail(key, code):
     rec = _record(key)
     raise RuntimeError(f"{rec.so[:-3]}: {getattr(_load(key), rec.strerror)(code).decode()} (code {code})")
@@ -521,6 +549,8 @@ tsru_lib = _accessor("tsru")
 tsru_check = _checker("tsru")
 cr_lib = _accessor("cr")
 cr_check = _checker("cr")
+zcr_lib = _accessor("zcr")
+zcr_check = _checker("zcr")
 
 
 # the paths as this import found them (tools and tests that inspect the files)

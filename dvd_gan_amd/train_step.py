@@ -48,6 +48,11 @@ Trainer(..., d_cr=lambda_real, d_cr_fake=lambda_fake) adds balanced consistency 
 Consistency Regularization for GANs") on those same transforms: in a D iteration every discriminator call takes the transformed
 views followed by the clean views of the same clips, and lambda * mean((D(T(x)) - D(x))^2) joins the network's loss (one more
 HIP launch per call, functional.CRLoss; the generator step is untouched); `cr_report()` is the one call that reads its statistics.
+Trainer(..., z_cr=lambda_dis, z_cr_gen=lambda_gen, z_cr_sigma=sigma) adds the paper's second regularizer, latent consistency
+regularization: the generator runs on [z | z + dz], dz ~ N(0, sigma^2), in ONE call on 2B rows; in a D iteration every fake call
+takes the views of both halves and z_cr * mean((D(v(G(z))) - D(v(G(z + dz))))^2) joins the network's loss (functional.CRLoss
+again); the generator step adds -z_cr_gen * mean((G(z) - G(z + dz))^2) over whole clips (functional.PairDistance: two streaming
+HIP launches forward, one backward); `zcr_report()` is the one call that reads its statistics.
 `evaluate_samples(real, n_samples=N, embed=...)` measures generation from noise (n_cond = 0): the Frechet and the kernel distance
 between features of real and of generated clips (distmetrics.py; the statistic of FVD / FID / KID, on the device).  `embed` is the
 caller's feature extractor or "Dt" / "Ds", this Trainer's own discriminator features -- comparable only under ONE fixed
@@ -174,6 +179,11 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
     d_cr = 0.0                    # weights of the consistency penalty on real / on generated clips (constructor keywords)
     d_cr_fake = 0.0
     _cr_stats = None              # fp32 [4][lib.CR_NSTAT]: D_s real / fake, D_t real / fake, when either weight is > 0
+    z_cr = 0.0                    # weights of latent consistency regularization on D_s / D_t and on G, scale of the perturbation
+    z_cr_gen = 0.0
+    z_cr_sigma = 0.03
+    _zcr_stats = None             # fp32 [2][lib.CR_NSTAT]: D_s, D_t fake calls, when z_cr or z_cr_gen is > 0 ...
+    _zcr_stats_g = None           # ... and fp32 [lib.ZCR_NSTAT] of the generator step
     _ema_block = False            # inside ema_weights()
     _epoch = 0                    # epochs train() has started
     _labels_registered = None     # register_label_buffer()'s tensor
@@ -182,7 +192,7 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
     g_optimizer = None
 
     def __init__(self, data_loader, config, device=None, compute_dtype=torch.bfloat16, latent_dim=4, dp_mode="replica", rnn="gru",
-                 tsru_flow=2.0, d_cr=0.0, d_cr_fake=None):
+                 tsru_flow=2.0, d_cr=0.0, d_cr_fake=None, z_cr=0.0, z_cr_gen=0.0, z_cr_sigma=0.03):
         """dp_mode (data-parallel runs only): "replica" = per-replica batch-norm statistics and condition rows, the
         semantics of the reference's nn.DataParallel (trainer.py:353-359); "global" = cross-replica conditional batch
         norm + gathered conditions: N ranks reproduce one process on the global batch.
@@ -193,7 +203,17 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
         same logit, L_D += d_cr * mean((D(T(x)) - D(x))^2) + d_cr_fake * mean((D(T(G(z))) - D(G(z)))^2).  0 = off; d_cr_fake =
         None takes d_cr.  They steer future steps only: neither the fingerprint nor the state file knows them.  In a data-parallel
         run the penalty is a mean over the rank's shard, which the gradient exchange turns into the mean over the global batch
-        when the shards are equal (unverified, like every other stabiliser there)."""
+        when the shards are equal (unverified, like every other stabiliser there).
+        z_cr, z_cr_gen, z_cr_sigma: latent consistency regularization of the same paper (its ICR = bCR + zCR).  With z' = z + dz,
+        dz ~ N(0, z_cr_sigma^2): in a D iteration L_D += z_cr * mean((D(v(G(z))) - D(v(G(z'))))^2) for each discriminator, v being
+        whatever the step applies to generated clips (frame sampling / downsampling, d_aug / d_aug_geom with the same frame ids
+        and table rows for both members of a pair); in the generator step L_G += -z_cr_gen * mean((G(z) - G(z'))^2) over all
+        elements of the B clips, before any view.  As reported for the paper's BigGAN runs: lambda_dis = 5, lambda_gen = 0.5,
+        sigma = 0.03.  0 / 0 = off (the default): nothing is allocated, drawn or launched.  With either weight > 0 the generator
+        runs on 2B rows [z | z'] in one call, dz is drawn from the noise generator right after z_class (draws["z_delta"] in a test),
+        and zcr_report() reads the statistics; sigma = 0 gives identical pairs.  The six returned losses do not change: the
+        generator's term is reported like ortho_penalty.  They steer future steps only (no fingerprint, no state: the noise
+        generator is saved already).  Data parallel as for d_cr: shard means averaged by the gradient exchange, unverified."""
         if dp_mode not in ("replica", "global"):
             raise ValueError("dp_mode must be 'replica' or 'global'")
         if rnn not in ("gru", "tsru"):
@@ -205,6 +225,11 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
         if not (0.0 <= d_cr < float("inf") and 0.0 <= d_cr_fake < float("inf")):
             raise ValueError(f"d_cr={d_cr}, d_cr_fake={d_cr_fake}: the consistency weights are finite and >= 0")
         self.d_cr, self.d_cr_fake = d_cr, d_cr_fake
+        z_cr, z_cr_gen, z_cr_sigma = float(z_cr), float(z_cr_gen), float(z_cr_sigma)
+        if not (0.0 <= z_cr < float("inf") and 0.0 <= z_cr_gen < float("inf") and 0.0 <= z_cr_sigma < float("inf")):
+            raise ValueError(f"z_cr={z_cr}, z_cr_gen={z_cr_gen}, z_cr_sigma={z_cr_sigma}: the latent consistency weights and the "
+                             "scale of the perturbation are finite and >= 0")
+        self.z_cr, self.z_cr_gen, self.z_cr_sigma = z_cr, z_cr_gen, z_cr_sigma
         self.rnn, self.tsru_flow = rnn, float(tsru_flow)
         self.dp_mode = dp_mode
         self.data_loader = data_loader
@@ -301,6 +326,9 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
                 self._anchors = torch.zeros(2, 2, 2, dtype=torch.float32, device=self.device)
         if self.d_cr > 0.0 or self.d_cr_fake > 0.0:
             self._cr_stats = torch.zeros(4, L.CR_NSTAT, dtype=torch.float32, device=self.device)
+        if self.z_cr > 0.0 or self.z_cr_gen > 0.0:
+            self._zcr_stats = torch.zeros(2, L.CR_NSTAT, dtype=torch.float32, device=self.device)
+            self._zcr_stats_g = torch.zeros(L.ZCR_NSTAT, dtype=torch.float32, device=self.device)
         Fn.direct_weight_grads(True)         # weight gradients accumulate into FlatAdam's buffers on a side stream
         self.exchange = GradExchange()
         # The step's dependent chain runs on a high-priority stream (ahead of the bulk weight-gradient stream) -- in a
@@ -485,16 +513,22 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
     def _site_loss(self, x, real_flag, site):
         return self.calc_loss(x, real_flag, _site=site) if self._adv_ex else self.calc_loss(x, real_flag)
 
-    def _d_pair(self, net, view, clean, labels, real_flag, site):
-        """One discriminator call of a D iteration with the consistency penalty on -> (adversarial term, penalty).  The
-        transformed views and the clean views of the same clips go through ONE call on a batch twice as long (both networks are
-        per-sample, no batch norm), so the spectral-norm vectors advance once per call as without the penalty.  The first half
-        of the logits is what the call returns today and goes through _site_loss unchanged; the penalty is
-        d_cr / d_cr_fake * mean((first - second)^2) (functional.CRLoss), its statistics row `site` of _cr_stats."""
-        out = net(torch.cat([view, clean]), torch.cat([labels, labels]))
-        n = out.numel() // 2
-        return (self._site_loss(out[:n], real_flag, site),
-                Fn.CRLoss.apply(out[:n], out[n:], self.d_cr if real_flag else self.d_cr_fake, self._cr_stats[site]))
+    def _d_pair(self, net, view, partners, labels, real_flag, site):
+        """One discriminator call of a D iteration with a consistency penalty on -> (adversarial term, sum of the penalties).
+        partners: a list of (clips, weight, statistics row), each a group the size of `view` that the network is asked to score
+        like `view` -- the clean views of the same clips (balanced consistency regularization: d_cr / d_cr_fake, a row of
+        _cr_stats), the views of the clips of the perturbed latents (latent consistency regularization: z_cr, a row of
+        _zcr_stats).  All groups go through ONE call on a batch 1 + len(partners) times as long (both networks are per-sample, no
+        batch norm), so the spectral-norm vectors advance once per call as without a penalty.  The first group's logits are what
+        the call returns today and go through _site_loss unchanged; each penalty is weight * mean((first - group)^2)
+        (functional.CRLoss)."""
+        out = net(torch.cat([view] + [p[0] for p in partners]), torch.cat([labels] * (1 + len(partners))))
+        n = out.numel() // (1 + len(partners))
+        penalty = None
+        for i, (_, weight, stats) in enumerate(partners):
+            term = Fn.CRLoss.apply(out[:n], out[(i + 1) * n:(i + 2) * n], weight, stats)
+            penalty = term if penalty is None else penalty + term
+        return self._site_loss(out[:n], real_flag, site), penalty
 
     def _end_d_iteration(self):
         """The anchors of the slot this D iteration wrote become those of the global batch (the update is linear in the batch
@@ -549,11 +583,15 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
         draws perm_real / z / z_class / perm_fake.  `hidden`: initial ConvGRU states for the generator
         (Generator.forward, frame-conditional variant).  With n_cond = K > 0 the clips are [B,3,K+T,H,W]: the first K frames
         condition the generator (`hidden` is then an error), perm_real / perm_fake draw over the T target frames, D_t sees
-        all K+T frames.  Returns the six loss terms as device scalars:
+        all K+T frames.  With z_cr or z_cr_gen on, `draws` also holds "z_delta" [B, z_dim], the perturbation of z itself.
+        Returns the six loss terms as device scalars:
         ds_real, ds_fake, dt_real, dt_fake, g_s, g_t.
         The step's dependent chain runs on a HIGH-priority stream so its (often small) launches are dispatched ahead of
         the bulk weight-gradient work queued on the normal-priority side stream; the caller's stream is ordered before
         and after the step, so nothing changes for it."""
+        if self._zcr_stats is not None and draws is not None:
+            for d in draws if isinstance(draws, (list, tuple)) else (draws,):
+                d["z_delta"]                                      # pinned draws pin the perturbation too: KeyError before any launch
         if self.n_cond:
             if hidden is not None:
                 raise ValueError("a frame-conditional Trainer (n_cond > 0) takes its generator states from the context frames, "
@@ -584,6 +622,7 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
         draws_all = draws
         aug, geo = bool(self.d_aug), bool(self.d_aug_geom)
         cr = self._cr_stats is not None
+        zcr = self._zcr_stats is not None
         tab_real = tab_fake = mat_real = mat_fake = None
         for _ in range(self.d_iters):
             if isinstance(draws_all, (list, tuple)):              # test aid: one dict of draws per discriminator iteration
@@ -621,7 +660,20 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
                     dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
                 for t_ in (real_videos, real_labels) + (tuple(t for t in (tab_real, mat_real) if t is not None) or (real_s,)):
                     t_.record_stream(self._aux)
-            fake_videos = self.G(z, z_class, hidden, cond=cond)
+            if zcr:
+                # latent consistency regularization: ONE generator call on [z | z + dz] (labels, context and states repeated), so
+                # the spectral-norm vectors and the batch-norm counters advance once; rows [:B] are the base clips (everything the
+                # step did with the generator's output, it does with them), rows [B:] their partners
+                z_delta = to_device_async(self.z_cr_sigma * torch.randn(self.batch_size, self.z_dim, generator=self.noise_gen)
+                                          if draws is None else torch.as_tensor(draws["z_delta"]), self.device)
+                B = z.shape[0]
+                twice = (lambda t: None if t is None else torch.cat([t, t]))
+                fake_both = self.G(torch.cat([z, z + z_delta]), twice(z_class),
+                                   None if hidden is None else [h if h is None else [twice(s) for s in h] for h in hidden],
+                                   cond=twice(cond))
+                fake_videos, fake_part = fake_both[:B], fake_both[B:].detach()
+            else:
+                fake_videos = self.G(z, z_class, hidden, cond=cond)
             ids_fake = draw_frame_ids(T, k, fg) if draws is None else torch.as_tensor(draws["perm_fake"])[:k].sort()[0]
             fake_in, cond_in = fake_videos, cond
             if aug or geo:
@@ -632,6 +684,9 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
                 if cond is not None:
                     cond_in = self._d_view(cond, mat_fake, tab_fake)
             fake_s = sample_k_frames(fake_in, T, k, ids_fake)
+            if zcr:
+                # the partners' views: the same table rows, the same frame ids (and below the same context views)
+                part_in = self._d_view(fake_part, mat_fake, tab_fake) if aug or geo else fake_part
             # ---------------- D_s
             if early:
                 cur.wait_stream(self._aux)
@@ -641,38 +696,60 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
                 # balanced consistency regularization: every discriminator call of the D iteration takes [transformed | clean]
                 # views of the same clips (the same frame ids), and the penalties join the network's loss before its one backward
                 ds_loss_real, ds_cr_real = self._d_pair(
-                    self.D_s, real_s, sample_k_frames(real_videos, T + Kc, k, ids_real + Kc if Kc else ids_real), real_labels, True, 0)
+                    self.D_s, real_s, [(sample_k_frames(real_videos, T + Kc, k, ids_real + Kc if Kc else ids_real), self.d_cr,
+                                        self._cr_stats[0])], real_labels, True, 0)
             else:
                 ds_loss_real = self._site_loss(self.D_s(real_s, real_labels), True, 0)
-            if cr:
-                fake_clean = fake_videos.detach()
-                ds_loss_fake, ds_cr_fake = self._d_pair(self.D_s, fake_s.detach(), sample_k_frames(fake_clean, T, k, ids_fake),
-                                                        z_class, False, 1)
+            if cr or zcr:
+                # the fake call's groups: [T(base) | clean base (d_cr_fake) | T(partners) (z_cr)]
+                partners = []
+                if cr:
+                    fake_clean = fake_videos.detach()
+                    partners.append((sample_k_frames(fake_clean, T, k, ids_fake), self.d_cr_fake, self._cr_stats[1]))
+                if zcr:
+                    partners.append((sample_k_frames(part_in, T, k, ids_fake), self.z_cr, self._zcr_stats[0]))
+                ds_loss_fake, ds_cr_fake = self._d_pair(self.D_s, fake_s.detach(), partners, z_class, False, 1)
             else:
                 ds_loss_fake = self._site_loss(self.D_s(fake_s.detach(), z_class), False, 1)
             self.reset_grad()
-            (ds_loss_real + ds_loss_fake + ds_cr_real + ds_cr_fake if cr else ds_loss_real + ds_loss_fake).backward()
+            ds_loss = ds_loss_real + ds_loss_fake
+            if cr:
+                ds_loss = ds_loss + ds_cr_real
+            if cr or zcr:
+                ds_loss = ds_loss + ds_cr_fake
+            ds_loss.backward()
             Fn.join_side()
             ex.start("Ds", self.ds_optimizer.grad)
             # ---------------- D_t (its forward/backward overlaps the D_s gradient exchange)
             fake_d = vid_downsample(fake_in) if cond is None else vid_downsample_cat(cond_in, fake_in)
             if cr:
-                # the clean view of the fake call is [raw context | generated]
-                dt_loss_real, dt_cr_real = self._d_pair(self.D_t, vid_downsample(real_in), vid_downsample(real_videos), real_labels,
-                                                        True, 2)
-                dt_loss_fake, dt_cr_fake = self._d_pair(
-                    self.D_t, fake_d.detach(), vid_downsample(fake_clean) if cond is None else vid_downsample_cat(cond, fake_clean),
-                    z_class, False, 3)
+                dt_loss_real, dt_cr_real = self._d_pair(self.D_t, vid_downsample(real_in),
+                                                        [(vid_downsample(real_videos), self.d_cr, self._cr_stats[2])], real_labels, True, 2)
+            elif not early:
+                real_d = vid_downsample(real_in)
+                dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
+            if cr or zcr:
+                partners = []
+                if cr:
+                    # the clean view of the fake call is [raw context | generated]
+                    partners.append((vid_downsample(fake_clean) if cond is None else vid_downsample_cat(cond, fake_clean),
+                                     self.d_cr_fake, self._cr_stats[3]))
+                if zcr:
+                    partners.append((vid_downsample(part_in) if cond is None else vid_downsample_cat(cond_in, part_in),
+                                     self.z_cr, self._zcr_stats[1]))
+                dt_loss_fake, dt_cr_fake = self._d_pair(self.D_t, fake_d.detach(), partners, z_class, False, 3)
             else:
-                if not early:
-                    real_d = vid_downsample(real_in)
-                    dt_loss_real = self._site_loss(self.D_t(real_d, real_labels), True, 2)
                 dt_loss_fake = self._site_loss(self.D_t(fake_d.detach(), z_class), False, 3)
             ex.finish("Ds")
             self.ds_optimizer.step()
             self.ds_lr_scher.step((ds_loss_real + ds_loss_fake) if self._plateau else None)
             self.dt_optimizer.zero_grad()
-            (dt_loss_real + dt_loss_fake + dt_cr_real + dt_cr_fake if cr else dt_loss_real + dt_loss_fake).backward()
+            dt_loss = dt_loss_real + dt_loss_fake
+            if cr:
+                dt_loss = dt_loss + dt_cr_real
+            if cr or zcr:
+                dt_loss = dt_loss + dt_cr_fake
+            dt_loss.backward()
             Fn.join_side()
             ex.start("Dt", self.dt_optimizer.grad)
             self._end_d_iteration()
@@ -703,7 +780,14 @@ class Trainer(TrainerState, TrainerSampling, TrainerReports):
                 ex.start_range("G", self.g_optimizer.grad, lo, self._g_hi, after=(Fn.side_stream_if_any(),))
                 self._g_hi = min(self._g_hi, lo)
             self.G.grad_ready_hook = on_ready
-        (g_s_loss + g_t_loss).backward()
+        if zcr and self.z_cr_gen > 0.0:
+            # the generator is asked not to map z and z + dz to the same clip: the one term that reads both halves of its output
+            (g_s_loss + g_t_loss + Fn.PairDistance.apply(fake_both, self.z_cr_gen, self._zcr_stats_g)).backward()
+        else:
+            if zcr:                                           # z_cr_gen = 0: the distances are still reported
+                with torch.no_grad():
+                    Fn.PairDistance.apply(fake_both.detach(), 0.0, self._zcr_stats_g)
+            (g_s_loss + g_t_loss).backward()
         Fn.join_side()
         if ex.active:
             self.G.grad_ready_hook = None

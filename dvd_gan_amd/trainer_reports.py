@@ -1,5 +1,5 @@
-"""What a Trainer reports about its run: the gradient guard's norms, the orthogonal penalty, the discriminators' logit statistics
-and the singular values of the weights.  A plain base class of train_step.Trainer; nothing here is on the training step's path
+"""What a Trainer reports about its run: the gradient guard's norms, the orthogonal penalty, the discriminators' logit statistics,
+the consistency penalties and the singular values of the weights.  A plain base class of train_step.Trainer; nothing here is on the training step's path
 but the device scalars the properties hand out, and each group has ONE call that synchronizes."""
 from . import lib as L
 
@@ -60,6 +60,23 @@ class TrainerReports(object):
         return {site: {"penalty": row[L.CR_STAT_PENALTY], "mean_sq_gap": row[L.CR_STAT_MSQ], "max_abs_gap": row[L.CR_STAT_MAXABS],
                        "nonzero": int(row[L.CR_STAT_NONZERO]), "n": int(row[L.CR_STAT_N])}
                 for site, row in zip(("Ds_real", "Ds_fake", "Dt_real", "Dt_fake"), s)}
+
+    def zcr_report(self):
+        """Latent consistency regularization of the last step as a host dict, or None when z_cr and z_cr_gen are both 0.  The one
+        call of this group that synchronizes.  "Ds" / "Dt": the penalty of the last D iteration's fake call as it entered the
+        network's loss, the mean squared gap between the logits of the base and of the partner clips, the largest |gap|, the pairs
+        whose gap is not zero and the number of pairs n (cr_report()'s five fields).  "G": the term as it entered the generator's
+        loss (-z_cr_gen * mean_sq_dist; zero while z_cr_gen = 0), the mean squared distance between base and partner clips, the
+        smallest and the largest per-pair mean squared distance (min_pair: the pair the generator moved least), the largest
+        |difference| of two elements, and the number of pairs."""
+        if self._zcr_stats is None:
+            return None
+        s, g = self._zcr_stats.cpu().tolist(), self._zcr_stats_g.cpu().tolist()
+        out = {tag: {"penalty": row[L.CR_STAT_PENALTY], "mean_sq_gap": row[L.CR_STAT_MSQ], "max_abs_gap": row[L.CR_STAT_MAXABS],
+                     "nonzero": int(row[L.CR_STAT_NONZERO]), "n": int(row[L.CR_STAT_N])} for tag, row in zip(("Ds", "Dt"), s)}
+        out["G"] = {"term": g[L.ZCR_STAT_TERM], "mean_sq_dist": g[L.ZCR_STAT_MSQ], "min_pair": g[L.ZCR_STAT_MIN_PAIR],
+                    "max_pair": g[L.ZCR_STAT_MAX_PAIR], "max_abs_diff": g[L.ZCR_STAT_MAXABS], "pairs": int(g[L.ZCR_STAT_PAIRS])}
+        return out
 
     # ---- singular values of the weights (spectral.py)
     def _sv_monitors(self):
