@@ -203,6 +203,7 @@ class GradSlot:
 
     def __init__(self):
         self.dx = None
+        self.task = -1          # autograd graph task in which the main branch last left its dx here (Conv.backward's guard)
 
 
 class Conv(Function):
@@ -253,6 +254,11 @@ class Conv(Function):
                     # engine pruned the main branch -- torch.autograd.grad(loss, [block.conv_sc.weight]) needs no d/dx of the block
                     # input, runs this node for its weight only and DISCARDS the dx computed here (needs_input_grad[0] is fixed at
                     # forward time).  Nothing is lost: dx is the shortcut's own term (tests/test_gpu_modules.py, pruned-graph case).
+                    # What is NOT legitimate: the main node ran in THIS backward pass (it stamps the slot with the graph task id) and
+                    # its dx is gone -- a term of the gradient would be dropped without a trace.
+                    if partner is None and ctx.slot.task >= 0 and ctx.slot.task == torch._C._current_graph_task_id():
+                        raise RuntimeError("GradSlot: the main branch ran in this backward pass but its input gradient is no longer "
+                                           "in the slot; the shortcut's dx would silently lose that term")
                 dx = K.conv_forward(dy, pk.wd, spec.ksize, pk.cip, mask=x if spec.relu_in else None, res=partner,
                                     wq=lambda: pk.fragment_major("wd"))
         wp, bp = ctx.params
@@ -367,6 +373,7 @@ class CondBatchNorm(Function):
         dx, dgb = K.cbn_backward(g.contiguous(), None, x, ctx.C_real, mean, rstd, gb, samp, ctx.relu, ctx.replicas)
         if ctx.slot is not None and ctx.needs_input_grad[0]:
             ctx.slot.dx, dx = dx, None                     # picked up (and added) by the shortcut conv's backward
+            ctx.slot.task = torch._C._current_graph_task_id()
         return dx, dgb, None, None, None, None, None, None, None, None, None, None, None, None
 
 
