@@ -1,5 +1,6 @@
 """ctypes binding of the shared libraries csrc/build.sh makes, one per header under include/: LIBRARIES (at the end) is the table of
-them, EXTENSIONS, MORE_EXTENSIONS and ZCR_EXTENSIONS the tables of the second family (xsrc/), _load() the one handshake of all.
+them, EXTENSIONS, MORE_EXTENSIONS, ZCR_EXTENSIONS and CLS_EXTENSIONS the tables of the second family (xsrc/), _load() the one handshake
+of all.
 Fails loudly: no fallback."""
 import ctypes as C
 import os
@@ -281,6 +282,22 @@ ZCR_SIGNATURES = {
     "dvdx_zcr_dist_grad": "i pp ll f p pp p",
 }
 
+# libdvdx_cls.so (include/dvdx_cls.h, CLS_EXTENSIONS below): the per-split sums of a classifier's logits behind the Inception Score
+# and the class-fidelity metrics (classmetrics.LogitStats)
+CLS_ABI_VERSION = 1
+CLS_F32, CLS_BF16, CLS_F16 = 0, 1, 2
+CLS_MAX_CLASSES, CLS_MAX_ROWS, CLS_MAX_SPLITS, CLS_MAX_TOTAL, CLS_ROW_BYTES, CLS_NSTAT = 4096, 1 << 20, 1024, 1 << 40, 40, 8
+(CLS_STAT_N, CLS_STAT_A, CLS_STAT_BAD, CLS_STAT_LABELLED, CLS_STAT_LOGLIK, CLS_STAT_TOP1, CLS_STAT_TOP5,
+ CLS_STAT_BAD_LABEL) = range(CLS_NSTAT)
+CLS_HEADER_CONSTANTS = {"DVDX_" + name: value for name, value in list(globals().items())
+                        if name.startswith("CLS_") and isinstance(value, int)}
+CLS_SIGNATURES = {
+    "dvdx_cls_abi_version": "i",
+    "dvdx_cls_strerror": "s i",
+    "dvdx_cls_ws_bytes": "l li",
+    "dvdx_cls_update": "i i pp li ll i pp pl p",
+}
+
 
 class SvItem(C.Structure):              # == dvd_sv_item
     _fields_ = [("W", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("state_off", C.c_longlong), ("ws_off", C.c_longlong),
@@ -445,15 +462,21 @@ ZCR_EXTENSIONS = {
                       strerror="dvdx_zcr_strerror"),
 }
 assert not (set(LIBRARIES) | set(EXTENSIONS) | set(MORE_EXTENSIONS)) & set(ZCR_EXTENSIONS)
+# ... and a fifth: tests/test_zcr_cpu.py fixes ZCR_EXTENSIONS to its one key and load_zcr_extensions() to its one handle.
+CLS_EXTENSIONS = {
+    "cls": _extension("cls", CLS_SIGNATURES, CLS_HEADER_CONSTANTS, abi=("dvdx_cls_abi_version", CLS_ABI_VERSION),
+                      strerror="dvdx_cls_strerror"),
+}
+assert not (set(LIBRARIES) | set(EXTENSIONS) | set(MORE_EXTENSIONS) | set(ZCR_EXTENSIONS)) & set(CLS_EXTENSIONS)
 _handles = {}           # key -> checked handle; _handles.pop(key, None) drops one, and the next accessor call loads it again
 
 
 def _record(key):
-    """The Library record of a key of any of the four tables."""
-    for table in (LIBRARIES, EXTENSIONS, MORE_EXTENSIONS):
+    """The Library record of a key of any of the five tables."""
+    for table in (LIBRARIES, EXTENSIONS, MORE_EXTENSIONS, ZCR_EXTENSIONS):
         if key in table:
             return table[key]
-    return ZCR_EXTENSIONS[key]
+    return CLS_EXTENSIONS[key]
 
 
 def library_path(key):
@@ -510,6 +533,11 @@ def load_zcr_extensions():
     return [_load(key) for key in ZCR_EXTENSIONS]
 
 
+def load_cls_extensions():
+    """Every library of CLS_EXTENSIONS, loaded and checked (__graft_entry__.build() calls it after load_zcr_extensions())."""
+    return [_load(key) for key in CLS_EXTENSIONS]
+
+
 def _fail(key, code):
     rec = _record(key)
     raise RuntimeError(f"{rec.so[:-3]}: {getattr(_load(key), rec.strerror)(code).decode()} (code {code})")
@@ -551,6 +579,8 @@ cr_lib = _accessor("cr")
 cr_check = _checker("cr")
 zcr_lib = _accessor("zcr")
 zcr_check = _checker("zcr")
+cls_lib = _accessor("cls")
+cls_check = _checker("cls")
 
 
 # the paths as this import found them (tools and tests that inspect the files)

@@ -375,6 +375,99 @@ class TrainerSampling(object):
             out.update({key: res[key] for key in ("precision", "recall", "density", "coverage")}, prdc_k=res["k"])
         return out
 
+    # ---- the Inception Score and class fidelity of generated clips under the caller's classifier (no counterpart in the reference;
+    # classmetrics.py)
+    @torch.no_grad()
+    def evaluate_classes(self, classifier, *, n_samples, labels=None, real=None, batch=None, splits=10, fidelity=True,
+                         confusion=False, use_ema=False, standing_stats=None, truncation=None, seed=0):
+        """Inception Score and class fidelity of n_samples clips generated from noise (n_cond = 0) under `classifier`: any callable
+        clips [B, 3, T, H, W] in [-1, 1] -> logits [B, C] (fp32, bf16 or fp16) on the device; a C3D network fine-tuned on UCF-101
+        gives the Inception Score video GANs publish.  The clips are conditioned on the first of: `labels` [n_samples]; the labels
+        of the first n_samples clips of `real` (a loader or any iterable of (clips [B, 3, T, H, W] in [-1, 1], labels [B]), which
+        must deliver that many); arange(n_samples) % n_class, balanced and drawn from nothing.  z comes from a private generator
+        seeded with `seed` (truncation as in sample()), `batch` clips at a time (default: batch_size), through the generator's
+        sampling path: eval mode, use_ema / standing_stats as in sample().  No logits are kept: every batch goes straight into a
+        classmetrics.LogitStats of `splits` splits.
+        fidelity=True compares the argmax with the conditioning labels (top1, top5, mean_log_lik; confusion=True: the matrix and
+        per_class_top1 too) and needs the classifier's classes to BE the generator's: a label >= C is a ValueError before anything
+        is generated.  C is learned from the first real batch when `real` is given, else from one call of the classifier on a single
+        all-zero clip.  fidelity=False serves a classifier over another label set (the Inception Score alone).
+        With `real` the same classifier scores the real clips against their own labels and their metrics come back as real_<key>:
+        the ceiling of every number here, which papers quote beside the generated one.
+        -> the dict of LogitStats.result() (is_mean, is_std, is_all, h_marginal, h_conditional, n, n_bad, n_bad_label, confusion,
+        with fidelity top1, top5, mean_log_lik, per_class_top1), the real_<key> entries and "n_classes".
+        Like evaluate_samples() the call leaves no trace: weights, spectral-norm u / v of all three networks, batch-norm statistics
+        and every random stream of the training run (noise_gen and torch's default generator included) are bit-equal before and
+        after."""
+        from . import classmetrics as CM
+        if self.n_cond:
+            raise RuntimeError("evaluate_classes() measures generation from noise (n_cond = 0); a frame-conditional Trainer has "
+                               "evaluate_prediction()")
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError(f"n_samples={n_samples}")
+        splits = int(splits)
+        if not 1 <= splits <= n_samples:
+            raise ValueError(f"splits={splits}: 1 to n_samples={n_samples}")
+        batch = int(self.batch_size if batch is None else batch)
+        if batch < 1:
+            raise ValueError(f"batch={batch}")
+        if confusion and not fidelity:
+            raise ValueError("confusion=True compares with the conditioning labels: it needs fidelity=True")
+        if labels is not None:
+            labels = self._check_labels(torch.as_tensor(labels).cpu().to(torch.long))
+            if labels.dim() != 1 or labels.shape[0] != n_samples:
+                raise ValueError(f"labels {tuple(labels.shape)} must hold n_samples={n_samples} class ids")
+        gen = torch.Generator().manual_seed(int(seed))
+
+        def score(stats, clips, y):
+            logits = classifier(clips)
+            if stats is None:
+                stats = CM.LogitStats(logits.shape[1], n_samples, splits=splits, confusion=confusion, device=self.device)
+            return stats.update(logits, y if fidelity else None)
+
+        out, n_classes = {}, None
+        if real is not None:
+            stats_r, real_labels, n_real = None, [], 0
+            rng_state = torch.get_rng_state()                  # a shuffling loader draws from the default generator
+            try:
+                for clips, y in real:
+                    take = min(clips.shape[0], n_samples - n_real)
+                    if take <= 0:
+                        break
+                    y = torch.as_tensor(y)[:take].cpu().to(torch.long)
+                    real_labels.append(y)
+                    stats_r = score(stats_r, to_device_async(clips[:take], self.device).to(torch.float32), y)
+                    n_real += take
+                    if n_real >= n_samples:
+                        break
+            finally:
+                torch.set_rng_state(rng_state)
+            if n_real < n_samples:
+                raise ValueError(f"`real` delivered {n_real} clips: n_samples={n_samples} are needed")
+            n_classes = stats_r.n_classes
+            out.update({"real_" + key: value for key, value in stats_r.result().items()})
+            if labels is None:
+                labels = self._check_labels(torch.cat(real_labels))
+        if labels is None:
+            labels = torch.arange(n_samples) % self.n_class
+        if fidelity:
+            if n_classes is None:
+                side = 16 * self.G.latent_dim
+                n_classes = classifier(torch.zeros(1, 3, self.n_frames, side, side, device=self.device)).shape[1]
+            if int(labels.max()) >= n_classes:
+                raise ValueError(f"fidelity=True: class id {int(labels.max())} has no logit among the classifier's {n_classes}; "
+                                 "fidelity=False scores a classifier over another label set")
+        stats = None
+        with self._sampling_weights(use_ema, standing_stats), self._g_eval():
+            for lo in range(0, n_samples, batch):
+                y = labels[lo:lo + batch]
+                z = self._draw_z(y.shape[0], truncation, gen)
+                fake = self.G(to_device_async(z, self.device), to_device_async(y, self.device))
+                stats = score(stats, fake.to(torch.float32).permute(0, 2, 1, 3, 4).contiguous(), y)
+        out.update(stats.result(), n_classes=stats.n_classes)
+        return out
+
     # ---- trainer.py:195-197, 323-334, 389-391: sample sheets (sheets.py)
     def fixed_inputs(self):
         """-> (fixed_z [n_class * test_batch_size, z_dim], fixed_label [n_class * test_batch_size]) on the device: the values of
