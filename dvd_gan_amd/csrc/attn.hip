@@ -151,10 +151,11 @@ __global__ __launch_bounds__(256) void attn_bwd_rows_kernel(const T* kv, int ldk
     (void)dgamma;                                  // dgamma: attn_dgamma_kernel below (fixed summation order)
     // dA[i][j] = gamma * sum_c dy[i][c] v[j][c]: the block's QB rows of dy are staged in LDS as
     // floats; thread j streams its v row with 16-byte loads and keeps QB accumulators.
-    float* dyl = S + QB * Nk;                       // [QB][C]
-    for (int idx = tid; idx < QB * C; idx += 256) {
-        const int i = idx / C, c = idx - i * C;
-        dyl[idx] = (i0 + i < N) ? ldf(dy + ((size_t)f * N + i0 + i) * ldx + c) : 0.f;
+    const int Cp = (C + 7) & ~7;                    // a ragged C (the forward takes any C <= ldx): zeros in [C, Cp)
+    float* dyl = S + QB * Nk;                       // [QB][Cp]
+    for (int idx = tid; idx < QB * Cp; idx += 256) {
+        const int i = idx / Cp, c = idx - i * Cp;
+        dyl[idx] = (i0 + i < N && c < C) ? ldf(dy + ((size_t)f * N + i0 + i) * ldx + c) : 0.f;
     }
     __syncthreads();
     for (int j = tid; j < Nk; j += 256) {
@@ -162,12 +163,16 @@ __global__ __launch_bounds__(256) void attn_bwd_rows_kernel(const T* kv, int ldk
 #pragma unroll
         for (int i = 0; i < QB; ++i) acc[i] = 0.f;
         const T* v = kf + (size_t)j * ldk + voff;
-        for (int c = 0; c < C; c += 8) {
+        for (int c = 0; c < Cp; c += 8) {
             float vv[8];
-            load8<T>(v + c, vv);                    // C is a multiple of 8, voff too
+            load8<T>(v + c, vv);                    // voff and ldk are multiples of 8: in bounds up to Cp
+            if (c + 8 > C) {                        // ragged C: the lanes behind C are not v (0 x Inf would be NaN)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) vv[k] = c + k < C ? vv[k] : 0.f;
+            }
 #pragma unroll
             for (int i = 0; i < QB; ++i) {
-                const float* d = dyl + i * C + c;
+                const float* d = dyl + i * Cp + c;
                 acc[i] += d[0] * vv[0] + d[1] * vv[1] + d[2] * vv[2] + d[3] * vv[3] + d[4] * vv[4] + d[5] * vv[5] +
                           d[6] * vv[6] + d[7] * vv[7];
             }
@@ -295,7 +300,7 @@ static int attention_fwd(int dtype, const void* q, int ldq, int dq, const void* 
 template <typename T>
 __global__ __launch_bounds__(256) void attn_dgamma_partial_kernel(const T* dy, const T* att_out, long long rows, int C, int ldx, float* partial) {
     __shared__ float shw[4];
-    const int cg = C / 8;
+    const int cg = (C + 7) / 8;
     float a = 0.f;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows * cg; i += (long long)gridDim.x * 256) {
         const long long r = i / cg;
@@ -304,7 +309,8 @@ __global__ __launch_bounds__(256) void attn_dgamma_partial_kernel(const T* dy, c
         load8<T>(dy + (size_t)r * ldx + c, u);
         load8<T>(att_out + (size_t)r * ldx + c, v);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) a += u[k] * v[k];
+        for (int k = 0; k < 8; ++k)
+            if (c + k < C) a += u[k] * v[k];           // (the pad lanes of dy are the caller's: not read as numbers)
     }
     a = wave_sum(a);
     if ((threadIdx.x & 63) == 0) shw[threadIdx.x >> 6] = a;
@@ -322,12 +328,15 @@ static int attention_bwd(int dtype, const void* q, int ldq, int dq, const void* 
                          int ldx, int C, const float* gamma, const void* att_out, const float* A, float* dS, void* dqo,
                          void* dkv, float* dgamma, long long frames, int N, int Nk, void* stream) {
     if (!q || !kv || !dy || !gamma || !att_out || !A || !dS || !dqo || !dkv || frames <= 0 || N <= 0 || Nk <= 0) return DVD_E_ARG;
-    if (frames > 65535 || (C & 7)) return DVD_E_SHAPE;
-    const int qb = ((size_t)16 * (Nk + C) * sizeof(float) <= 64 * 1024 && (size_t)16 * N * sizeof(float) <= 64 * 1024) ? 16 : 8;
-    if ((size_t)qb * (Nk + C) * sizeof(float) > 64 * 1024) return DVD_E_SHAPE;
+    if (frames > 65535 || dq <= 0 || C <= 0) return DVD_E_SHAPE;
+    // what the forward takes (16-byte vectors; any C <= ldx: a ragged C used to pass the forward and fail here, in the backward pass)
+    if ((ldq & 7) || (ldk & 7) || (ldx & 7) || (koff & 7) || (voff & 7) || C > ldx) return DVD_E_SHAPE;
+    const int Cp = (C + 7) & ~7;
+    const int qb = ((size_t)16 * (Nk + Cp) * sizeof(float) <= 64 * 1024 && (size_t)16 * N * sizeof(float) <= 64 * 1024) ? 16 : 8;
+    if ((size_t)qb * (Nk + Cp) * sizeof(float) > 64 * 1024) return DVD_E_SHAPE;
     const int nr = (int)std::min<size_t>((size_t)N, 64 * 1024 / (qb * sizeof(float)));      // query rows per column-pass chunk
     dim3 grid_r(cdiv(N, qb), (unsigned)frames), grid_c(cdiv(Nk, qb), (unsigned)frames);
-    const size_t sh_rows = (size_t)qb * (Nk + C) * sizeof(float), sh_cols = (size_t)qb * nr * sizeof(float);
+    const size_t sh_rows = (size_t)qb * (Nk + Cp) * sizeof(float), sh_cols = (size_t)qb * nr * sizeof(float);
 #define ATT_BWD(QB_)                                                                                                    \
     do {                                                                                                                \
         BY_DTYPE(dtype, attn_bwd_rows_kernel<T, QB_><<<grid_r, 256, sh_rows, S_>>>((const T*)kv, ldk, dq, koff, voff,   \

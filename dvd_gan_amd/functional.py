@@ -300,6 +300,10 @@ class Pool(Function):
 
     @staticmethod
     def forward(ctx, x, pt):
+        if pt != 1 and (x.dim() != 5 or x.shape[1] % pt):
+            # H and W may be odd (unpool zero-fills the line the floor dropped, out_hw); a dropped FRAME it cannot put back
+            raise ValueError(f"Pool: pt={pt} on {tuple(x.shape)}: the temporal extent must be a multiple of pt (the backward "
+                             f"pass cannot restore floored frames)")
         ctx.pt, ctx.hw = pt, (x.shape[-3], x.shape[-2])
         return K.pool(x, pt)
 
@@ -778,6 +782,9 @@ class MaxPool3d(Function):
 
     @staticmethod
     def forward(ctx, x):
+        if x.dim() != 5 or (x.shape[1] | x.shape[2] | x.shape[3]) & 1:
+            # the backward kernel writes whole 2 x 2 x 2 windows only: an odd tail of dx would stay uninitialised
+            raise ValueError(f"MaxPool3d: {tuple(x.shape)} is not [F, T, H, W, C] with even T, H and W")
         F_, T, H, W, ld = x.shape
         y = torch.empty(F_, T // 2, H // 2, W // 2, ld, dtype=x.dtype, device=x.device)
         L.check(L.lib().dvd_maxpool3d(L.dt(x), L.ptr(x), L.ptr(y), F_, T // 2, H // 2, W // 2, ld, L.stream()))

@@ -232,6 +232,16 @@ def mfma_case(name, F, N, C, regime, g, seed, ldq=None):
     if g == 0.0:
         assert same_bits(y, x), name + ": y != x with gamma = 0"
     w = Worst(name)
+    dsum, dmag = mfma_bounds(w, F, N, C, g, qkv, x, dy, y, att, lse, D, dqkv)
+    w.add("dgamma", abs(float(dgamma) - (0.375 + dsum)) / (C_MFMA["dgamma"] * E32 * (dmag + 0.375)))
+    w.check(C_MFMA)
+
+
+def mfma_bounds(w, F, N, C, g, qkv, x, dy, y, att, lse, D, dqkv):
+    """The elementwise checks of the MFMA kernels' outputs (q | k | v at 0 | 16 | 32 of qkv [F, N, ldq]; x, dy, y, att [F, N, C];
+    lse, D [F, N]; dqkv like qkv) added to the Worst `w`; lse = None / D = None: that buffer is not at hand (a caller that sees
+    only what the autograd Function keeps) and its check is left out -- the bounds of the others do not change.  Returns
+    (sum, sum of magnitudes) of dy * att_out, the terms of dgamma."""
     dsum, dmag = 0.0, 0.0
     for f0, f1 in frame_chunks(F, N * N):
         q, k, v, s, m, lse_r, A, out, y_r = ref_forward(qkv, qkv, x, g, 16, 16, 32, C, f0, f1)
@@ -248,11 +258,13 @@ def mfma_case(name, F, N, C, regime, g, seed, ldq=None):
         w.add("y", ratio(y[f0:f1], y_r, C_MFMA["y"] * abs(g) * (E16 * (av + f32_att) + f32_att)
                          + 2 * E32 * ((g * out).abs() + x[f0:f1].double().abs()), torch.bfloat16))
         b_lse = C_MFMA["lse"] * E32 * (qk.amax(-1) + lse_r[..., 0].abs() + 1)
-        w.add("lse", ratio(lse[f0:f1], lse_r[..., 0], b_lse, torch.float32))
+        if lse is not None:
+            w.add("lse", ratio(lse[f0:f1], lse_r[..., 0], b_lse, torch.float32))
         dyd, atd = dy[f0:f1].double(), att[f0:f1].double()
         D_r = (dyd * atd).sum(-1)
         Dmag = (dyd * atd).abs().sum(-1)
-        w.add("D", ratio(D[f0:f1], D_r, C_MFMA["D"] * E32 * Dmag, torch.float32))
+        if D is not None:
+            w.add("D", ratio(D[f0:f1], D_r, C_MFMA["D"] * E32 * Dmag, torch.float32))
         dsum += float(D_r.sum())
         dmag += float(Dmag.sum())
         dp = dyd @ v.transpose(1, 2)
@@ -274,8 +286,7 @@ def mfma_case(name, F, N, C, regime, g, seed, ldq=None):
                                                                               + (A * sigb).transpose(1, 2) @ dyd.abs()
                                                                               + 2 * E32 * (A.transpose(1, 2) @ dyd.abs())),
                           torch.bfloat16))
-    w.add("dgamma", abs(float(dgamma) - (0.375 + dsum)) / (C_MFMA["dgamma"] * E32 * (dmag + 0.375)))
-    w.check(C_MFMA)
+    return dsum, dmag
 
 
 MFMA_CASES = {
@@ -328,7 +339,7 @@ def f32_case(name, dtype, F, N, Nk, dq, C, ldx, regime, g, seed, self_attn=True)
     dcode = L.dt(torch.empty(0, dtype=dtype))
     koff = (dq + 7) // 8 * 8
     voff = 2 * koff
-    ldq = ldk = voff + C if self_attn else (voff + C + 7) // 8 * 8
+    ldq = ldk = (voff + C + 7) // 8 * 8
     qb, kvb, x, dy = make_case(F, N, Nk, dq, koff, voff, C, ldq, ldk, ldx, dtype, regime, self_attn, seed)
     gamma = torch.tensor([g], device=DEV)
     args = (dcode, qb, kvb, x, dy, gamma, dq, koff, voff, C, F, N, Nk, self_attn)
@@ -342,7 +353,9 @@ def f32_case(name, dtype, F, N, Nk, dq, C, ldx, regime, g, seed, self_attn=True)
     nb = 256 if F * N * Nk >= 256 else 1                        # dgamma partials at the head of dS (attention_bwd)
     assert same_bits(dS.flatten()[nb:], dS2.flatten()[nb:]), name + ": rerun of dS differs"
     assert same_bits(dgamma, dgamma2), name + ": rerun of dgamma differs"
-    assert bool(torch.isnan(y[..., C:].float()).all() and torch.isnan(att[..., C:].float()).all()), name + ": pad columns of y"
+    C8 = (C + 7) // 8 * 8            # a ragged last 8-lane group is stored whole: zeros behind C; whole pad groups are not written
+    assert bool(torch.isnan(y[..., C8:].float()).all() and torch.isnan(att[..., C8:].float()).all()), name + ": pad columns of y"
+    assert bool((y[..., C:C8] == 0).all() and (att[..., C:C8] == 0).all()), name + ": pad lanes of the last channel group"
     if self_attn:
         check_columns(dqo, [(0, dq), (koff, dq), (voff, C)], name + " dqkv")
     else:
@@ -351,6 +364,16 @@ def f32_case(name, dtype, F, N, Nk, dq, C, ldx, regime, g, seed, self_attn=True)
     if g == 0.0:
         assert same_bits(y[..., :C], x[..., :C]), name + ": y != x with gamma = 0"
     w = Worst(name)
+    dsum, dmag = f32_bounds(w, dtype, F, N, Nk, dq, koff, voff, C, g, qb, kvb, x, dy, y, att, A, dS, dqo, dkv)
+    w.add("dgamma", abs(float(dgamma) - (0.375 + dsum)) / (C_F32["dgamma"] * E32 * (dmag + 0.375)))
+    w.check(C_F32)
+
+
+def f32_bounds(w, dtype, F, N, Nk, dq, koff, voff, C, g, qb, kvb, x, dy, y, att, A, dS, dqo, dkv):
+    """The elementwise checks of the fp32 attention kernels' outputs added to the Worst `w`: q at [0, dq) of qb [F, N, ldq], k | v
+    at koff | voff of kvb [F, Nk, ldk]; x, dy, y, att [F, N, ldx]; A, dS [F, N, Nk]; dqo like qb, dkv like kvb (one buffer for self
+    attention).  dS = None: not at hand (scratch of the autograd Function's backward), its check is left out.  Returns (sum, sum of
+    magnitudes) of dy * att_out, the terms of dgamma."""
     dsum, dmag = 0.0, 0.0
     for f0, f1 in frame_chunks(F, N * Nk):
         q, k, v, s, m, lse_r, A_r, out, y_r = ref_forward(qb, kvb, x, g, dq, koff, voff, C, f0, f1)
@@ -369,7 +392,8 @@ def f32_case(name, dtype, F, N, Nk, dq, C, ldx, regime, g, seed, self_attn=True)
         mag_dS = magA * (dA - Dp).abs() + A_r * (math.sqrt(C) * abs(g) * (dyd.abs() @ v.abs().transpose(1, 2))
                                                   + math.sqrt(Nk) * (A_r * dA.abs()).sum(-1, keepdim=True)
                                                   + (magA * dA.abs()).sum(-1, keepdim=True))
-        w.add("dS", ratio(dS[f0:f1], dS_r, C_F32["dS"] * E32 * mag_dS + TINY * ((dA - Dp).abs() + 1), torch.float32))
+        if dS is not None:
+            w.add("dS", ratio(dS[f0:f1], dS_r, C_F32["dS"] * E32 * mag_dS + TINY * ((dA - Dp).abs() + 1), torch.float32))
         dq_r, dk_r, dv_r = dS_r @ k, dS_r.transpose(1, 2) @ q, g * A_r.transpose(1, 2) @ dyd
         aS = dS_r.abs()
         w.add("dq", ratio(dqo[f0:f1, :, :dq], dq_r, C_F32["dq"] * E32 * (mag_dS @ k.abs() + math.sqrt(Nk) * (aS @ k.abs())), dtype))
@@ -380,8 +404,7 @@ def f32_case(name, dtype, F, N, Nk, dq, C, ldx, regime, g, seed, self_attn=True)
         terms = dyd * att[f0:f1, :, :C].double()
         dsum += float(terms.sum())
         dmag += float(terms.abs().sum())
-    w.add("dgamma", abs(float(dgamma) - (0.375 + dsum)) / (C_F32["dgamma"] * E32 * (dmag + 0.375)))
-    w.check(C_F32)
+    return dsum, dmag
 
 
 F32, BF16 = torch.float32, torch.bfloat16
@@ -403,6 +426,9 @@ F32_CASES = {
     "one_partial_gamma0_f32": dict(dtype=F32, F=1, N=8, Nk=8, dq=8, C=16, ldx=16, regime="units", g=0.0, seed=39),
     "one_partial_gamma0_bf16": dict(dtype=BF16, F=3, N=8, Nk=8, dq=8, C=16, ldx=16, regime="units", g=0.0, seed=40),
     "one_partial_f32": dict(dtype=F32, F=2, N=8, Nk=8, dq=8, C=16, ldx=16, regime="large", g=1.2, seed=41),
+    # C no multiple of 8 (the forward takes any C <= ldx, the backward must too): the last 8-lane group of v and dy is ragged
+    "ragged_C20_ldx24_f32": dict(dtype=F32, F=3, N=16, Nk=16, dq=2, C=20, ldx=24, regime="units", g=0.7, seed=42),
+    "ragged_C20_ldx24_bf16": dict(dtype=BF16, F=3, N=40, Nk=40, dq=2, C=20, ldx=24, regime="onehot", g=-0.8, seed=43),
 }
 
 
@@ -418,6 +444,9 @@ KV_CASES = {
     # the size-128 geometry: 48 x 8 x 8 = 3072 queries, 384 keys (the column pass walks the queries in two LDS chunks)
     "gen128_3072x384_f32": dict(dtype=F32, F=2, N=3072, Nk=384, dq=128, C=256, ldx=256, regime="last", g=0.7, seed=53),
     "gen128_3072x384_bf16": dict(dtype=BF16, F=2, N=3072, Nk=384, dq=128, C=256, ldx=256, regime="onehot", g=0.7, seed=54),
+    # C no multiple of 8 on the kv entry points
+    "ragged_C20_ldx24_f32": dict(dtype=F32, F=2, N=32, Nk=4, dq=4, C=20, ldx=24, regime="units", g=0.7, seed=55),
+    "ragged_C20_ldx24_bf16": dict(dtype=BF16, F=2, N=32, Nk=4, dq=4, C=20, ldx=24, regime="large", g=0.9, seed=56),
 }
 
 
@@ -514,6 +543,21 @@ def sep_case(name, dtype, B, T, W, H, Cq, C, axis, g, seed, ties=False, bchunk=8
     assert same_bits(dgamma, dgamma2), name + ": rerun of dgamma differs"
     check_columns(got["dqkv"], [(0, Cq), (koff, Cq), (voff, C)], name + " dqkv")
     w = Worst(name)
+    dsum, dmag, ntie_k, ntie_v = sep_bounds(w, name, dtype, B, T, W, H, Cq, koff, voff, C, axis, g, qkv, x, dy, got, bchunk)
+    w.add("dgamma", abs(float(dgamma) - (0.375 + dsum)) / (C_SEP["dgamma"] * E32 * (dmag + 0.375)))
+    if ties:
+        note(f"{name} tied k pairs along T", ntie_k)
+        note(f"{name} tied v pairs along T", ntie_v)
+        assert ntie_k > 0 and ntie_v > 0, f"{name}: no tied max-pool pairs ({ntie_k} k, {ntie_v} v)"
+    w.check(C_SEP)
+
+
+def sep_bounds(w, name, dtype, B, T, W, H, Cq, koff, voff, C, axis, g, qkv, x, dy, got, bchunk=8):
+    """The checks of the separable cell's outputs added to the Worst `w`.  got: y, Qf, Kp, Vp, ksel, vsel, att, dqkv as
+    dvd_sepattn_forward / backward leave them (flat scratch buffers as the entry points take them).  Returns (sum, sum of magnitudes
+    of the dgamma terms, tied k pairs, tied v pairs along T)."""
+    N = T * W * H
+    A = (T, W, H)[axis]
     L = Cq * N // A
     dsum, dmag, ntie_k, ntie_v = 0.0, 0.0, 0, 0
     for b0 in range(0, B, bchunk):
@@ -551,12 +595,7 @@ def sep_case(name, dtype, B, T, W, H, Cq, C, axis, g, seed, ties=False, bchunk=8
         w.l2("dv" + tag, dq[..., voff:voff + C], r["dv"])
         dsum += float(r["dgamma"].sum())
         dmag += float(r["dgamma"].abs().sum())
-    w.add("dgamma", abs(float(dgamma) - (0.375 + dsum)) / (C_SEP["dgamma"] * E32 * (dmag + 0.375)))
-    if ties:
-        note(f"{name} tied k pairs along T", ntie_k)
-        note(f"{name} tied v pairs along T", ntie_v)
-        assert ntie_k > 0 and ntie_v > 0, f"{name}: no tied max-pool pairs ({ntie_k} k, {ntie_v} v)"
-    w.check(C_SEP)
+    return dsum, dmag, ntie_k, ntie_v
 
 
 SEP_CASES = {
